@@ -61,6 +61,20 @@ vct_comm_*: checked bit-equal to the torch frame and timed).
 rehearses the N-rank plumbing on the CPU (gloo, a pattern-writing stand-in
 for the trace; nothing is measured, value = null).
 
+A plain run does what the metric needs and no more: K1-K3 once, the G-buffer, the
+counting frame (the frame's cone steps), the K4 form and the stream overlap settled,
+the warmup, the K timed steps, one line (`metric`, `value`, `unit`, `ms_per_step`, ...,
+`k4_form`, `overlap_tune`).  Everything else described above -- the K1-K3 timings and
+rooflines, the K4 launch alone and `roofline`, `latency`, `timed_equals_counting`,
+`cpu_baseline`, `frame_loop`, `stress`, `secondary`, `multi_config`, the parts of a
+step and `capi` at N > 1 -- is measured and reported only with `--full`.
+
+`--dump-outputs DIR` writes the last timed frame as its caller receives it
+(FrameTracer.diff / .spec after drain(), on rank 0) to DIR/diffuse.npy and DIR/spec.npy
+(float32).  A frame of more than 2^20 pixels is written as a fixed sample of 2^20
+pixels (seed 0; their flat indices in DIR/sample_pixels.npy).  Scene, light, camera and
+G-buffer are procedural and seeded, so equal arguments give equal inputs on every run.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -124,6 +138,15 @@ def parse():
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--profile-json", default=PROFILE)
     p.add_argument("--dry-run", action="store_true", help="CPU rehearsal of the rank plumbing (gloo), no GPU")
+    p.add_argument("--full", action="store_true",
+                   help="everything beside the metric too: K1-K3 timings and rooflines, the K4 launch alone and its "
+                        "roofline, timed == counting check, CPU baseline, frame loop, stress, secondary scene, "
+                        "multi_config, the parts of a step and the C-ABI leg at N > 1 (--secondary, --stress, "
+                        "--frame-loop, --multi-config, --cpu-seconds, --no-cpu-baseline, --profile-json act only here)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last timed frame (what FrameTracer hands its caller) as "
+                        "DIR/diffuse.npy and DIR/spec.npy (float32; a fixed seeded pixel sample, listed in "
+                        "DIR/sample_pixels.npy, when the frame exceeds the size cap)")
     a = p.parse_args()
     if a.reorder:
         a.variant |= 0x8000
@@ -415,6 +438,27 @@ def emit(obj):
         os.write(_JSON_FD, line.encode())
 
 
+DUMP_MAX_PX = 1 << 20      # pixels per plane written whole; a larger frame is sampled (2 planes x 16 MiB + the list)
+
+
+def write_outputs(path, diff, spec):
+    """--dump-outputs: the last timed frame's two planes ([h][w][4] float32 host arrays) as
+    <path>/diffuse.npy and <path>/spec.npy.  A frame of more than DUMP_MAX_PX pixels is
+    written as the same DUMP_MAX_PX pixels every run (seed 0, ascending; their flat indices
+    y * w + x in sample_pixels.npy, float64), [DUMP_MAX_PX][4] per plane."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    d, s = diff.reshape(-1, 4), spec.reshape(-1, 4)
+    if d.shape[0] > DUMP_MAX_PX:
+        px = np.sort(np.random.default_rng(0).choice(d.shape[0], DUMP_MAX_PX, replace=False))
+        d, s = d[px], s[px]
+        np.save(os.path.join(path, "sample_pixels.npy"), px.astype(np.float64))
+    else:
+        d, s = d.reshape(diff.shape), s.reshape(spec.shape)
+    np.save(os.path.join(path, "diffuse.npy"), np.ascontiguousarray(d, dtype=np.float32))
+    np.save(os.path.join(path, "spec.npy"), np.ascontiguousarray(s, dtype=np.float32))
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "0") or 0)
@@ -582,13 +626,17 @@ def relight_roofline(ctx, n, scene, k1_ms, k2_ms, k3_ms, k3_sparse=False):
 
 
 def measure_scene(args, torch, dist, ctx, scene_name, rank, world, dev, stream, counting_only=False,
-                  relight_roofs=False):
-    """K1-K3 for `scene_name`, the G-buffer, one counting frame, then K timed frames."""
+                  relight_roofs=False, dump=False):
+    """K1-K3 for `scene_name`, the G-buffer, one counting frame, then K timed frames.
+    Without --full only what the metric needs: K1-K3 run once (untimed), the counting frame
+    gives the frame's cone steps, and nothing follows the timed frames.  `dump`: the last
+    timed frame goes to the host on the rank that holds it (`_dump`, for --dump-outputs)."""
     import numpy as np
     from vct import scenes
     from vct.camera import Camera
     from vct.multi import FrameTracer, compact_index
     n, w, h = args.n, args.width, args.height
+    full = args.full
 
     def timed(fn):
         torch.cuda.synchronize()
@@ -616,18 +664,20 @@ def measure_scene(args, torch, dist, ctx, scene_name, rank, world, dev, stream, 
     dgeo = (torch.from_numpy(v).to(dev), torch.from_numpy(i.astype(np.int32)).to(dev),
             torch.from_numpy(m.astype(np.int32)).to(dev), torch.from_numpy(k).to(dev))
     ctx.voxelize_device(*dgeo)
-    r = {"k1_voxelize_ms": round(timed(lambda: ctx.voxelize_device(*dgeo)), 3)}
+    r = {"k1_voxelize_ms": round(timed(lambda: ctx.voxelize_device(*dgeo)), 3)} if full else {}
     del dgeo
     level0 = torch.empty((n ** 3 * 4,), dtype=torch.float32, device=dev)
     k2_ms = 0.0
     if rank == 0:
         ctx.inject_directional(scenes.LIGHT_DIR, scenes.LIGHT_COLOR)
-        k2_ms = timed_queued(lambda: ctx.inject_directional(scenes.LIGHT_DIR, scenes.LIGHT_COLOR))
+        if full:
+            k2_ms = timed_queued(lambda: ctx.inject_directional(scenes.LIGHT_DIR, scenes.LIGHT_COLOR))
         ctx.copy_level0_to_device(level0)
     bcast_ms, k2_rep_ms, k2_rep_match = 0.0, k2_ms, True
     if world > 1:
         dist.barrier()
         bcast_ms = timed(lambda: dist.broadcast(level0, src=0))
+    if world > 1 and full:
         # SURVEY 8e alternative to the broadcast: every rank runs K2 itself (K2 is
         # deterministic, so the replicated grid must equal the broadcast one bit for bit)
         if rank != 0:
@@ -639,27 +689,29 @@ def measure_scene(args, torch, dist, ctx, scene_name, rank, world, dev, stream, 
             del mine
         k2_rep_ms, mism = max_over_ranks(torch, dist, dev, [k2_rep_ms, 0.0 if k2_rep_match else 1.0], world)
         k2_rep_match = mism == 0.0
+    if world > 1:
         ctx.set_level0_from_device(level0)
     del level0
     ctx.build_mips()
-    k3_ms = timed_queued(ctx.build_mips)
+    k3_ms = timed_queued(ctx.build_mips) if full else 0.0
     # world 1: level 0 came from K2, so those were relight builds (Grid::k3_live).  With more
     # ranks the broadcast level 0 is a dense write (full builds); the replicated-K2 frame
     # (every rank injects itself) gets relight builds: timed here after a local injection
     # (level 0 equals the broadcast one bit for bit, replicated_k2_equals_bcast)
     k3_rep_ms = k3_ms
-    if world > 1:
+    if world > 1 and full:
         ctx.inject_directional(scenes.LIGHT_DIR, scenes.LIGHT_COLOR)
         ctx.build_mips()
         k3_rep_ms = max_over_ranks(torch, dist, dev, [timed_queued(ctx.build_mips)], world)[0]
-    r.update({"k2_inject_ms": round(k2_ms, 3), "k3_mips_ms": round(k3_ms, 3), "grid_bcast_ms": round(bcast_ms, 3),
-              "k3_mips_relight_ms": round(k3_rep_ms, 3)})
-    if relight_roofs:
+    if full:
+        r.update({"k2_inject_ms": round(k2_ms, 3), "k3_mips_ms": round(k3_ms, 3), "grid_bcast_ms": round(bcast_ms, 3),
+                  "k3_mips_relight_ms": round(k3_rep_ms, 3)})
+    if relight_roofs and full:
         # world 1: level 0 comes from K2 here, so the timed builds are relight builds; with
         # more ranks it arrived through set_level0_from_device (a dense write: full builds)
         r.update(relight_roofline(ctx, n, scene_name, r["k1_voxelize_ms"], k2_ms, k3_ms, k3_sparse=world == 1))
 
-    progress(rank, f"  {scene_name}: K1-K3 timed")
+    progress(rank, f"  {scene_name}: K1-K3 {'timed' if full else 'done'}")
     cam = Camera()
     eye = [float(x) for x in cam.position]
     if args.gbuffer == "scene":
@@ -682,11 +734,13 @@ def measure_scene(args, torch, dist, ctx, scene_name, rank, world, dev, stream, 
     local_steps, local_texels = int(cnt[0].item()), int(cnt[1].item())
     # the counting frame's planes: the timed frames (another compiled form, no counters,
     # perhaps reordered or dispatched longest first) must equal them bit for bit
-    lp = tracer.local_planes(0)
-    counted = None if lp is None else (lp[0].clone(), lp[1].clone())
-    valid = (gb[0][..., 3] != 0).reshape(-1).cpu().numpy()
-    fi, _ = compact_index(w, h, rank, world)
-    local_valid = int(valid[fi].sum())
+    counted, local_valid = None, 0
+    if full:
+        lp = tracer.local_planes(0)
+        counted = None if lp is None else (lp[0].clone(), lp[1].clone())
+        valid = (gb[0][..., 3] != 0).reshape(-1).cpu().numpy()
+        fi, _ = compact_index(w, h, rank, world)
+        local_valid = int(valid[fi].sum())
     tot = torch.tensor([local_steps, local_valid], dtype=torch.int64, device=dev)
     if world > 1:
         dist.all_reduce(tot)
@@ -715,6 +769,14 @@ def measure_scene(args, torch, dist, ctx, scene_name, rank, world, dev, stream, 
     elapsed = time.perf_counter() - t0
     elapsed = max_over_ranks(torch, dist, dev, [elapsed], world)[0]
     progress(rank, f"  {scene_name}: {args.steps} timed frames done")
+    ms_per_step = elapsed / args.steps * 1e3
+    r.update({"value": frame_steps * args.steps / elapsed / 1e6, "ms_per_step": ms_per_step,
+              "frame_cone_steps": frame_steps, "overlap": tracer.overlap})
+    if dump and rank == 0 and tracer.holds_frame:
+        # the last timed frame as the tracer's caller reads it (drained above), before anything overwrites it
+        r["_dump"] = (tracer.diff.cpu().numpy(), tracer.spec.cpu().numpy())
+    if not full:
+        return r
     lp = tracer.local_planes(tracer.last_buf)       # the last timed frame (drained above)
     last = None if lp is None else (lp[0].clone(), lp[1].clone())   # compared after the K4-alone loop
     k4_ov_ms = [a.elapsed_time(b) for a, b in ev]
@@ -743,11 +805,9 @@ def measure_scene(args, torch, dist, ctx, scene_name, rank, world, dev, stream, 
     del counted, last
     k4_avg_ms = sum(k4_ms) / len(k4_ms)
     k4_med_ms = sorted(k4_ms)[len(k4_ms) // 2]
-    ms_per_step = elapsed / args.steps * 1e3
     r.update({
-        "value": frame_steps * args.steps / elapsed / 1e6, "ms_per_step": ms_per_step, "frame_cone_steps": frame_steps,
         "valid_px": frame_valid, "k4_kernel_ms_avg": k4_avg_ms, "k4_kernel_ms_median": k4_med_ms,
-        "k4_kernel_ms_avg_overlapped": sum(k4_ov_ms) / len(k4_ov_ms), "overlap": tracer.overlap,
+        "k4_kernel_ms_avg_overlapped": sum(k4_ov_ms) / len(k4_ov_ms),
         "k4_kernel_ms_min": min(k4_ms), "k4_kernel_ms_max": max(k4_ms),
         "local_texels": local_texels, "local_valid": local_valid, "local_steps": local_steps,
         "frame_relight_ms": round(min(k2_ms + bcast_ms + k3_ms, k2_rep_ms + k3_rep_ms) + ms_per_step, 3),
@@ -1040,13 +1100,20 @@ def run(args, world):
     ctx.set_stream(stream.cuda_stream)
 
     progress(rank, f"metric workload: {args.scene} {n}^3 {w}x{h}, {world} rank(s)")
-    m = measure_scene(args, torch, dist, ctx, args.scene, rank, world, dev, stream, relight_roofs=rank == 0)
+    m = measure_scene(args, torch, dist, ctx, args.scene, rank, world, dev, stream, relight_roofs=rank == 0,
+                      dump=bool(args.dump_outputs))
     progress(rank, f"metric done: {m['value']:.0f} Mcone-steps/s")
-    key = profile_key(n, w, h, args.scene, args.gbuffer, args.n_diffuse, spec, args.variant, world)
-    rec, reason = load_profile(args.profile_json, key)
-    roof = roofline(rec, reason, m["k4_kernel_ms_avg"], m["local_texels"], m["local_valid"], args.profile_json, key,
-                    steps=m["local_steps"])
-    if roof.get("frac") is not None and m["ms_per_step"] > 0:
+    if "_dump" in m:
+        write_outputs(args.dump_outputs, *m.pop("_dump"))
+        progress(rank, f"last timed frame written to {args.dump_outputs}")
+    full = args.full
+    roof = None
+    if full:
+        key = profile_key(n, w, h, args.scene, args.gbuffer, args.n_diffuse, spec, args.variant, world)
+        rec, reason = load_profile(args.profile_json, key)
+        roof = roofline(rec, reason, m["k4_kernel_ms_avg"], m["local_texels"], m["local_valid"], args.profile_json,
+                        key, steps=m["local_steps"])
+    if full and roof.get("frac") is not None and m["ms_per_step"] > 0:
         # the same per-launch work over the pipelined frame time: with frame overlap a launch's
         # own start-to-end time includes the other frame's share of the chip, so the rate the
         # timed loop sustains is work per frame / ms per step
@@ -1078,8 +1145,13 @@ def run(args, world):
                 "exchange": args.exchange if world > 1 else None, "variant": args.variant,
             },
         }
-        for k_ in ("frame_cone_steps", "valid_px"):
-            result[k_] = m[k_]
+        result["full"] = full
+        result["frame_cone_steps"] = m["frame_cone_steps"]
+        result["frame_overlap"] = "two trace streams" if m["overlap"] else "one stream"
+        result["overlap_tune"] = m["overlap_tune"]
+        result["k4_form"] = form_name(m["k4_form"])
+    if rank == 0 and full:
+        result["valid_px"] = m["valid_px"]
         # latency beside throughput: `value` pipelines consecutive frames (frame f+1's trace
         # fills the tail of frame f's launch), so a launch inside the loop runs longer from
         # start to end than alone; a renderer that presents each frame before tracing the
@@ -1118,12 +1190,12 @@ def run(args, world):
             host = tuple(t_.cpu().numpy() for t_ in m["_gb"])
             result["cpu_baseline"] = cpu_baseline(ctx, n, g0, E, host, m["_eye"], args.n_diffuse, spec,
                                                   m["_steps_px"].cpu().numpy().astype(np.uint32), args.cpu_seconds)
-    if world == 1 and args.frame_loop:
+    if full and world == 1 and args.frame_loop:
         loop_scene = frame_loop(torch, ctx, m["_gb"], w, h, m["_eye"], stream, args.frame_loop, variant=args.variant)
         result["frame_loop"] = {f"G_{args.gbuffer}": loop_scene}
         progress(rank, "frame loop done")
     capi = None
-    if world > 1:
+    if full and world > 1:
         if os.environ.get("VCT_DIST_BACKEND", "nccl") == "nccl":
             # a failure on any rank (the C-ABI returns VCT_ECOMM after its deadline and aborts
             # its communicator) is recorded, agreed on over the torch group, and the line goes on
@@ -1151,7 +1223,7 @@ def run(args, world):
     del m
     torch.cuda.empty_cache()
     st = (args.stress or "").strip()
-    if st == "rand" and world == 1 and args.gbuffer == "scene":
+    if full and st == "rand" and world == 1 and args.gbuffer == "scene":
         progress(rank, "stress (G_rand)")
         result["stress"] = stress_rand(args, torch, ctx, dev, stream)
         loop = result["stress"].pop("_loop")
@@ -1159,7 +1231,7 @@ def run(args, world):
             result["frame_loop"]["G_rand"] = loop
         torch.cuda.empty_cache()
     sec = (args.secondary or "").strip()
-    if sec and sec != "none" and sec != args.scene:
+    if full and sec and sec != "none" and sec != args.scene:
         # the same size on a non-flat scene (varied normals: fewer combined-face bricks)
         progress(rank, f"secondary: {sec}")
         s2 = measure_scene(args, torch, dist, ctx, sec, rank, world, dev, stream)
@@ -1183,7 +1255,7 @@ def run(args, world):
     ctx.close()
     torch.cuda.empty_cache()
     mc = [c.strip() for c in (args.multi_config or "").split(",") if c.strip() and c.strip() != "none"]
-    if mc:
+    if full and mc:
         out = {}
         for name in mc:
             cfg = MULTI_CONFIGS[name]

@@ -69,6 +69,43 @@ def test_roofline_from_profile(tmp_path):
     assert r["frac"] is None and r["note"]
 
 
+def test_write_outputs(tmp_path, monkeypatch):
+    """bench.write_outputs (--dump-outputs): a frame within the cap is written whole; a
+    larger one as the same seeded pixel sample every time, its flat indices beside it;
+    float32 planes either way."""
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+    h, w = 13, 21
+    rng = np.random.default_rng(5)
+    diff, spec = (rng.random((h, w, 4), dtype=np.float32) for _ in range(2))
+    bench.write_outputs(str(tmp_path / "whole"), diff, spec)
+    assert sorted(os.listdir(tmp_path / "whole")) == ["diffuse.npy", "spec.npy"]
+    d, s = np.load(tmp_path / "whole" / "diffuse.npy"), np.load(tmp_path / "whole" / "spec.npy")
+    assert d.dtype == s.dtype == np.float32 and np.array_equal(d, diff) and np.array_equal(s, spec)
+    monkeypatch.setattr(bench, "DUMP_MAX_PX", 100)
+    for name in ("a", "b"):
+        bench.write_outputs(str(tmp_path / name), diff, spec)
+    px = np.load(tmp_path / "a" / "sample_pixels.npy")
+    assert px.dtype == np.float64 and px.shape == (100,) and np.array_equal(px, np.load(tmp_path / "b" / "sample_pixels.npy"))
+    idx = px.astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < h * w
+    d, s = np.load(tmp_path / "a" / "diffuse.npy"), np.load(tmp_path / "a" / "spec.npy")
+    assert d.dtype == s.dtype == np.float32
+    assert np.array_equal(d, diff.reshape(-1, 4)[idx]) and np.array_equal(s, spec.reshape(-1, 4)[idx])
+
+
+def test_full_is_off_by_default(monkeypatch):
+    sys.path.insert(0, REPO)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "1"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 4
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
 def test_k3_relight_bytes():
     """bench.k3_relight_bytes: a relight K3 build reads / writes the first launch's bytes
     only for blocks (16 x 16 x 8 level-0 voxels at the default depth) holding an occupied

@@ -12,6 +12,7 @@ echo "pytest rc=$rc"; tail -5 gpurun_out/pytest_gpu.log
 if faulted gpurun_out/pytest_gpu.log; then echo "GPU FAULT in tests"; exit 99; fi
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 if [ -n "$SKIP_BENCH" ]; then exit $rc; fi
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 timeout -k 10 ${BENCH_TIMEOUT:-400} python bench.py --steps $STEPS --warmup 2 ${BENCH_ARGS:-} > gpurun_out/bench.json 2> gpurun_out/bench.err
 brc=$?
 echo "bench rc=$brc"; cat gpurun_out/bench.json; tail -5 gpurun_out/bench.err
@@ -23,6 +24,7 @@ if [ -n "$EXTRA" ]; then
   i=0
   for xa in "${XS[@]}"; do
     i=$((i+1))
+    xa="--full $xa"
     timeout -k 10 ${BENCH_TIMEOUT:-400} python bench.py --no-cpu-baseline $xa > gpurun_out/bench_x$i.json 2> gpurun_out/bench_x$i.err
     xrc=$?
     echo "extra[$i] ($xa) rc=$xrc"; cat gpurun_out/bench_x$i.json | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['k4_kernel_ms_avg'], d['roofline']['frac'])" 2>/dev/null

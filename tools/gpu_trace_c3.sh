@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 TAG=${TAG:-r4}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace --output-format csv -- python3 bench.py --steps 50 --overlap off --no-cpu-baseline --secondary none --stress none --multi-config none --frame-loop 0 > $OUT/c3.json 2> $OUT/c3.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace --output-format csv -- python3 bench.py --full --steps 50 --overlap off --no-cpu-baseline --secondary none --stress none --multi-config none --frame-loop 0 > $OUT/c3.json 2> $OUT/c3.err
 rc=$?; echo "rocprof rc=$rc"; [ $rc -eq 0 ] || { tail -5 $OUT/c3.err; exit $rc; }
 find $OUT/trace -name "*kernel_stats.csv" -exec cp {} $OUT/c3_kernel_stats.csv \;
 python3 - $OUT <<'PY'

@@ -12,7 +12,7 @@ for L in "$@"; do
   mkdir -p $out
   echo "$L" > $out/lib.txt
   VCT_LIB=$L timeout -s KILL ${PASS_TIMEOUT:-120} rocprofv3 --pmc $PMC -d $out -o p --output-format csv -- \
-      python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --secondary none > $out/stdout 2> $out/stderr
+      python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --secondary none > $out/stdout 2> $out/stderr
   rc=$?
   echo "$L rc=$rc"
   if [ $rc -ne 0 ]; then tail -5 $out/stderr; exit $rc; fi

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 TAG=${TAG:-r1}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
-BARGS=${BENCH_ARGS:-"--steps 10 --warmup 2 --no-cpu-baseline"}
+BARGS=${BENCH_ARGS:-"--full --steps 10 --warmup 2 --no-cpu-baseline"}
 faulted() { grep -qE "HSA_STATUS_ERROR|Memory access fault|APERTURE_VIOLATION" "$@"; }
 run() {  # name, rocprof args...
   local name=$1; shift
