@@ -398,4 +398,8 @@ vct_status vct_dump_info(const char* stem, vct_config* cfg, uint32_t* what);
 #ifdef __cplusplus
 }
 #endif
+
+/* ---- light bounces (additive; HIP library only) ---------------------------------- */
+#include "vct_bounce.h"
+
 #endif /* VCT_H */

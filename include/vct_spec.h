@@ -146,4 +146,28 @@
 #define VCT_CLEAR_B         0.3f
 #define VCT_INV_GAMMA       0.454545468f /* 1 / 2.2 */
 
+/* ---- light bounces (vct_inject_bounces, include/vct_bounce.h; no new literals) ------
+ * L0 = the level-0 radiance at the call (K2's output), A / N = K1's resolved albedo and
+ * normal grids, g0, E, n = the grid.
+ *  Sources: every occupied voxel whose resolved normal is not (0,0,0).  Occupied voxels
+ *    with a zero normal (two-sided thin geometry whose normals cancel) receive no bounce
+ *    and keep L0; empty voxels stay +0.
+ *  The source at integer voxel (x,y,z) is the G-buffer record
+ *      hh  = E / (float)n                                 (float divide)
+ *      P_c = g0_c + ((float)x_c + 0.5f) * hh              (multiply, then add; no fma)
+ *      P.w = 1, normal = N[v].xyz, albedo = A[v].rgb      (roughness unused)
+ *    and the bounce gather is K4 (A.5, A.6) on that record with the context's diffuse
+ *    cone set (n_diffuse, aniso) and no specular cone, whatever cfg.specular is.  The
+ *    cone origin is therefore (P - g0) * inv_h + N as A.5 computes it from a world
+ *    position, not x + 0.5 (the round trip through P is inexact for ~40 % of the voxels
+ *    of a 32^3 grid).
+ *  One bounce (Jacobi): I_k = K4.diffuse.rgb gathered from the pyramid built from L_k;
+ *      L_{k+1}.rgb = L0.rgb + A.rgb * I_k.rgb             (one multiply, one add per channel)
+ *      L_{k+1}.a   = L0.a
+ *    at every source.  Every bounce adds to L0, never to L_k; no gather sees another
+ *    voxel's update of the same bounce (level 0 is not written while the gather runs);
+ *    after each bounce the pyramid is rebuilt from L_{k+1}.  Level 0 stays nonzero
+ *    exactly at the occupied voxels (alpha), so the relight mip build stays legal.
+ *  n_diffuse = 0: I = 0 and L stays L0. */
+
 #endif /* VCT_SPEC_H */

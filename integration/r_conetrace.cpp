@@ -189,6 +189,7 @@ void ConeTraceRenderer::Render()
 		if (!Check(vct_inject_directional(ctx_, light_dir_, light_color_), "vct_inject_directional") ||
 		    !Check(vct_build_mips(ctx_), "vct_build_mips"))
 			return;
+		if (bounces && !Check(vct_inject_bounces(ctx_, bounces), "vct_inject_bounces")) return;
 		light_dirty_ = false;
 	}
 	// the active camera in the reference's conventions: lookAt (camera.cpp:24-27),

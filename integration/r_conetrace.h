@@ -30,6 +30,10 @@ public:
 	// a new directional light: the next frame relights (K2 + K3) without voxelizing again
 	void SetLight(const float dir_to_light[3], const float color[3]);
 
+	// light bounces added to the grid after each inject + build (vct_inject_bounces;
+	// 0: the grid holds direct light only).  Takes effect with the next relight.
+	unsigned bounces = 0;
+
 	bool Ok() const { return ok_; }
 
 private:

@@ -326,6 +326,7 @@ void vct_destroy(vct_ctx* c) {
     if (c->step_tab) (void)hipFree(c->step_tab);
     if (c->spec_keys) (void)hipFree(c->spec_keys);
     if (c->spec_rows) (void)hipFree(c->spec_rows);
+    bounce_free(c);
     for (auto& s : c->scratch)
         if (s.p) (void)hipFree(s.p);
     for (auto& ss : c->k4s)
@@ -410,7 +411,7 @@ static vct_status voxelize_dev(vct_ctx* c, const void* dv, uint32_t stride, uint
     // if a step below fails part way (K1 has already rewritten the accumulators, the
     // occupied list and level 0 by then): only the success path sets `voxelized` again
     Grid& g = c->grid;
-    g.voxelized = g.injected = g.mipped = false;
+    g.voxelized = g.injected = g.mipped = g.bounced = false;
     g.k2_coarse_ok = g.k3_sparse_ok = g.zm_valid = false;
     g.k3_live_bz = 0;
     ++c->grid_epoch;
@@ -562,8 +563,67 @@ vct_status vct_inject_directional(vct_ctx* c, const float dir[3], const float co
     if (st != VCT_OK) return st;
     VCT_HIP(launch_inject(c, lx, ly, lz, color[0], color[1], color[2]), "inject");
     c->grid.injected = true;
+    c->grid.bounced = false;
     c->grid.mipped = false;
     c->grid.l0_on_peers = false;
+    return VCT_OK;
+}
+
+vct_status vct_inject_bounces(vct_ctx* c, uint32_t n_bounces) {
+    if (!c) return VCT_EINVAL;
+    Grid& g = c->grid;
+    if (!g.voxelized) return fail(c, VCT_ESTATE, "inject_bounces before voxelize");
+    if (!g.injected || !g.mipped) return fail(c, VCT_ESTATE, "inject_bounces before inject / build_mips");
+    if (n_bounces == 0) return VCT_OK;
+    if (g.bounced)
+        return fail(c, VCT_ESTATE, "inject_bounces twice on one level 0 (inject or upload a new one first)");
+    vct_status st = use_device(c);
+    if (st != VCT_OK) return st;
+    VCT_HIP(bounce_sources(c), "bounce sources");
+    g.bounced = true;
+    Bounce& b = c->bounce;
+    // no cone (I = 0) or no source: level 0 and its mips stay as they are
+    if (c->cfg.n_diffuse == 0 || b.n_src == 0) return VCT_OK;
+    VCT_HIP(launch_bounce_save(c), "bounce: level-0 copy");
+    for (uint32_t i = 0; i < n_bounces; ++i) {
+        const bool timed = b.profile && i + 1 == n_bounces;
+        if (timed) {
+            for (hipEvent_t& ev : b.ev)
+                if (!ev) VCT_HIP(hipEventCreate(&ev), "event create");
+            VCT_HIP(hipEventRecord(b.ev[0], c->stream), "event record");
+        }
+        // Jacobi: the gather reads the pyramid of L_k, level 0 included; it is written only
+        // after it (stream order), always as L0 + A * I_k
+        VCT_HIP(launch_bounce_gather(c), "bounce: gather");
+        if (timed) VCT_HIP(hipEventRecord(b.ev[1], c->stream), "event record");
+        VCT_HIP(launch_bounce_accumulate(c), "bounce: accumulate");
+        if (timed) VCT_HIP(hipEventRecord(b.ev[2], c->stream), "event record");
+        g.mipped = false;
+        g.l0_on_peers = false;
+        if (i + 1 < n_bounces) {
+            // between bounces only this device gathers: its pyramid alone (a relight build
+            // where the last build was one: level 0 is still nonzero exactly at the occupied voxels)
+            VCT_HIP(launch_mips(c), "bounce: mips");
+            g.mipped = true;
+        } else if ((st = vct_build_mips(c)) != VCT_OK) {
+            return st;
+        }
+        if (timed) {
+            VCT_HIP(hipEventRecord(b.ev[3], c->stream), "event record");
+            VCT_HIP(hipEventSynchronize(b.ev[3]), "event synchronize");
+            for (int j = 0; j < 3; ++j) VCT_HIP(hipEventElapsedTime(&b.ms[j + 1], b.ev[j], b.ev[j + 1]), "event time");
+        }
+    }
+    return VCT_OK;
+}
+
+vct_status vct_bounce_sources(vct_ctx* c, uint32_t* n_sources) {
+    if (!c || !n_sources) return c ? fail(c, VCT_EINVAL, "bounce_sources: null output") : VCT_EINVAL;
+    if (!c->grid.voxelized) return fail(c, VCT_ESTATE, "bounce_sources before voxelize");
+    vct_status st = use_device(c);
+    if (st != VCT_OK) return st;
+    VCT_HIP(bounce_sources(c), "bounce sources");
+    *n_sources = c->bounce.n_src;
     return VCT_OK;
 }
 
@@ -910,6 +970,7 @@ vct_status vct_upload_level0(vct_ctx* c, const float* host) {
     VCT_HIP(launch_relayout(c, (const float4*)tmp, c->grid.pyr, c->grid.n, false), "relayout");
     VCT_HIP(hipStreamSynchronize(c->stream), "sync");
     c->grid.injected = true;
+    c->grid.bounced = false;
     c->grid.l0_dense = true;
     c->grid.mipped = false;
     c->grid.l0_on_peers = false;
@@ -923,6 +984,7 @@ vct_status vct_level0_device(vct_ctx* c, void** dptr, size_t* bytes) {
     if (bytes) *bytes = (size_t)c->grid.n * c->grid.n * c->grid.n * 16;
     // the caller (e.g. an RCCL broadcast) writes level 0 behind our back
     c->grid.injected = true;
+    c->grid.bounced = false;
     c->grid.l0_dense = true;
     c->grid.mipped = false;
     c->grid.l0_on_peers = false;
@@ -945,6 +1007,7 @@ vct_status vct_set_level0_from_device(vct_ctx* c, const void* src) {
     const size_t nv = (size_t)c->grid.n * c->grid.n * c->grid.n;
     VCT_HIP(hipMemcpyAsync(c->grid.pyr, src, nv * 16, hipMemcpyDeviceToDevice, c->stream), "copy level0 in");
     c->grid.injected = true;
+    c->grid.bounced = false;
     c->grid.l0_dense = true;
     c->grid.mipped = false;
     c->grid.l0_on_peers = false;

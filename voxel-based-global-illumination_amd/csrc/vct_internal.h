@@ -68,6 +68,7 @@ struct Grid {
     bool voxelized = false, injected = false, mipped = false;
     bool l0_dense = false;   // level 0 was replaced densely (upload / device copy): K2 must clear it whole
     bool l0_on_peers = false;   // multi-device: the other devices hold this level 0 (vct_build_mips copies it)
+    bool bounced = false;       // vct_inject_bounces has added to this level 0 (cleared with every new level 0)
 };
 
 struct Mesh {
@@ -89,6 +90,34 @@ struct Textures {
 struct Scratch {
     void* p = nullptr;
     size_t bytes = 0;
+};
+
+// Light bounces (vct_bounce.hip; vct_spec.h "light bounces").  The sources of a
+// voxelization -- occupied voxels with a nonzero normal -- are kept as a materialised
+// G-buffer that K4 traces like a frame of 64 * tiles_x by 64 * tiles_y pixels: source s
+// sits at the pixel that lane s % 64 of K4's unit s / 64 traces (bounce_pixel), so a wave
+// holds 64 consecutive sources, and the sources are listed region by region (16^3 voxels,
+// Morton order inside), so those 64 are neighbours.  Pixels past the last source are
+// background records (P.w = 0).  84 bytes per source: position, normal, K4's two outputs,
+// the level 0 the bounces add to, and the voxel index.  Built on the first use after a
+// voxelization or load (one count is read back), reused by every relight.
+struct Bounce {
+    bool built = false;
+    uint32_t epoch = 0;              // vct_ctx::grid_epoch the list belongs to
+    uint32_t n_src = 0;
+    uint32_t tiles_x = 0, tiles_y = 0;
+    uint32_t* vox = nullptr;         // [n_src] linear-Z voxel of source s
+    float4* l0 = nullptr;            // [n_src] level 0 before the first bounce
+    float4* gbuf = nullptr;          // [4][px]: position, normal, diffuse out, specular out
+    uint32_t* region = nullptr;      // [regions + 1] sources per region, then their prefix sums
+    size_t src_cap = 0, l0_cap = 0, px_cap = 0, region_cap = 0;
+    int form = 0;                    // the compiled K4 form the gather launches (0 union, 1 occupancy;
+                                     // atrium 256^3: 0.754 against 0.791 ms, tools/bounce_bench.py)
+    int order = 1;                   // 1 region runs, 0 occ_list order (vct_debug_bounce, A/B: 0.754
+                                     // against 1.534 ms per gather)
+    bool profile = false;            // vct_debug_bounce: time the stages with events
+    hipEvent_t ev[4] = {};
+    float ms[4] = {0, 0, 0, 0};      // list build, gather, accumulate, K3 of the last bounce
 };
 
 // K4's per-launch scratch, one set per stream: K4 launches on different streams may run
@@ -197,6 +226,7 @@ struct vct_ctx {
                                   // 8 multi-device tiles / gather, 9 multi-device step counters)
     vct::StreamScratch k4s[vct::kStreamSets];   // K4 hand-over + reorder scratch per stream (k4_scratch)
     vct::K4Tuner k4tune;                // timed-form choice of the default cone trace
+    vct::Bounce bounce;                 // source list of vct_inject_bounces
     uint32_t grid_epoch = 0;            // bumped by every voxelization (a new scene for the tuner)
     vct::StepRow* step_tab = nullptr;   // [kMaxStepRows] diffuse-cone step table (device)
     unsigned* spec_keys = nullptr;      // [2 * kSpecSlots]: specular table keys (~0u free), then states
@@ -252,7 +282,19 @@ hipError_t launch_k3_live(vct_ctx* c);
 // one nl^3 face volume between the pyramid's texel layout and linear-Z (vct_device.h)
 hipError_t launch_relayout(vct_ctx* c, const float4* src, float4* dst, uint32_t nl, bool to_linear);
 // K4
-hipError_t launch_trace(vct_ctx* c, const vct_trace_args* a);
+// bounce_form >= 0: the gather of vct_inject_bounces -- the diffuse cone set only, whatever
+// cfg.specular says, in that compiled form (0 union, 1 occupancy), screen order, without
+// the tuner, the longest-first dispatch or the debug schedule; the tuner's state (and
+// vct_trace_form) is left as it was
+hipError_t launch_trace(vct_ctx* c, const vct_trace_args* a, int bounce_form = -1);
+// light bounces (vct_bounce.hip): the source list of the current voxelization (built when
+// c->bounce is stale; synchronises the ctx stream once to read the count back), the copy of
+// level 0 the bounces add to, one gather (K4 over the sources), and level 0 = L0 + A * I
+hipError_t bounce_sources(vct_ctx* c);
+hipError_t launch_bounce_save(vct_ctx* c);
+hipError_t launch_bounce_gather(vct_ctx* c);
+hipError_t launch_bounce_accumulate(vct_ctx* c);
+void bounce_free(vct_ctx* c);
 // ray reordering (variant 0x8000, vct_reorder.hip): *perm = the frame's pixels sorted by the
 // Morton code of their cone origin's voxel, background last (device, w * h entries)
 // (perm_spec, nullable: a second order for the specular part, by cell and cone aperture)

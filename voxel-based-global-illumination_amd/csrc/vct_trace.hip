@@ -1712,7 +1712,8 @@ static int k4_form(vct_ctx* c, uint64_t key, const int* cands_in, int n_in, bool
     return f;
 }
 
-hipError_t launch_trace(vct_ctx* c, const vct_trace_args* a) {
+hipError_t launch_trace(vct_ctx* c, const vct_trace_args* a, int bounce_form) {
+    const bool bounce = bounce_form >= 0;     // the gather of vct_inject_bounces (vct_internal.h)
     const Grid& g = c->grid;
     TraceK k;
     k.pyr = g.pyr;
@@ -1739,7 +1740,7 @@ hipError_t launch_trace(vct_ctx* c, const vct_trace_args* a) {
     k.world = (int)world;
     k.compact = a->tile_compact ? 1 : 0;
     k.nd = (int)c->cfg.n_diffuse;
-    k.spec_on = c->cfg.specular ? 1 : 0;
+    k.spec_on = (c->cfg.specular && !bounce) ? 1 : 0;
     k.aniso = g.aniso;
     k.tau_d = c->cfg.n_diffuse == 16 ? VCT_TAN20 : VCT_TAN30;
     k.steps_tab = c->step_tab;
@@ -1761,8 +1762,8 @@ hipError_t launch_trace(vct_ctx* c, const vct_trace_args* a) {
     }
     k.sc_part = k.sc_cone = nullptr; k.sc_flag = nullptr; k.sc_px = 0;
     k.perm = k.perm_spec = nullptr;
-    k.order = c->k4_dbg_order;
-    k.dur = c->k4_dbg_dur;
+    k.order = bounce ? nullptr : c->k4_dbg_order;
+    k.dur = bounce ? nullptr : c->k4_dbg_dur;
     k.npx = a->width * a->height;
     k.zmap = g.zm_valid ? g.zmap : nullptr;
     k.zm_levels = g.zm_valid ? g.zm_levels : 0;
@@ -1785,7 +1786,9 @@ hipError_t launch_trace(vct_ctx* c, const vct_trace_args* a) {
     const bool cnt_form = counting || (a->variant & kVarCountingForm);
     int cand = 0;
     hipEvent_t* ev = nullptr;
-    {
+    if (bounce) {
+        cand = bounce_form & 1;
+    } else {
         int forms[2], nf = 0, orders[2], no = 0;
         if (a->variant & VCT_VARIANT_FORCE_UNION) forms[nf++] = 0;
         else if (a->variant & VCT_VARIANT_FORCE_OCCUPANCY) forms[nf++] = 1;
@@ -1862,7 +1865,7 @@ hipError_t launch_trace(vct_ctx* c, const vct_trace_args* a) {
         c->n_cu = 0;
     const bool lpt_size = c->n_cu > 0 && blocks <= (uint32_t)c->n_cu * 4u * kOccWaves * kLptMaxGenerations;
     const uint32_t per_class = (blocks + 7u) / 8u;   // units of residue class 0, the largest
-    if (deflt && !cnt_form && !(a->variant & kVarNoLpt) && c->k4tune.cur >= 0 && !c->k4_dbg_order && !c->k4_dbg_dur &&
+    if (deflt && !bounce && !cnt_form && !(a->variant & kVarNoLpt) && c->k4tune.cur >= 0 && !c->k4_dbg_order && !c->k4_dbg_dur &&
         per_class <= kLptMaxPerClass && !c->k4tune.multi && (lpt_size || (a->variant & kVarLptAll))) {
         K4Tuner::Entry& te = c->k4tune.e[c->k4tune.cur];
         if (te.chosen >= 0) {
@@ -1927,7 +1930,7 @@ hipError_t launch_trace(vct_ctx* c, const vct_trace_args* a) {
             }
             if (ev) (void)hipEventRecord(ev[1], c->stream);
             K4Tuner& T = c->k4tune;
-            if (deflt && !cnt_form && T.multi && (T.prev_end || hipEventCreateWithFlags(&T.prev_end,
+            if (deflt && !bounce && !cnt_form && T.multi && (T.prev_end || hipEventCreateWithFlags(&T.prev_end,
                                                                           hipEventDisableTiming) == hipSuccess))
                 (void)hipEventRecord(T.prev_end, c->stream);
         }

@@ -4,12 +4,15 @@
 // dumps the last one as a PPM instead of swapping buffers.
 //
 //   vct_headless <model.obj> [grid=256] [width=800] [height=600] [frames=5] [out.ppm] [devices=1]
-//                [--model=reference|identity] [--grid=fit|unit]
+//                [--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32]
 //   (devices > 1: one process drives that many GPUs through vct_create_multi)
 //   --model: the model matrix of the reference's draw, T(0,-1.75,0) S(0.2)
 //            (r_voxelization.cpp:26-29; default), or none;
 //   --grid:  the cubic grid around the placed model's bounds with one voxel of
 //            padding (default), or [-1,1]^3 padded by one voxel (unit-box scenes).
+//   --bounces: light bounces added to the grid after each inject + build
+//            (vct_inject_bounces; default 0);
+//   --linear: also dump the last frame before tone mapping (raw float32 [h][w][4]).
 #include <cstdio>
 #include <cstdlib>
 #include <memory>
@@ -23,18 +26,24 @@ using namespace vcthost;
 int main(int argc, char** argv) {
     std::vector<std::string> pos;
     bool ref_model = true, fit_grid = true;
+    int bounces = 0;
+    std::string linear;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--model=reference") ref_model = true;
         else if (a == "--model=identity") ref_model = false;
         else if (a == "--grid=fit") fit_grid = true;
         else if (a == "--grid=unit") fit_grid = false;
+        else if (a == "--bounces" && i + 1 < argc) bounces = std::atoi(argv[++i]);
+        else if (a.rfind("--bounces=", 0) == 0) bounces = std::atoi(a.c_str() + 10);
+        else if (a.rfind("--linear=", 0) == 0) linear = a.substr(9);
         else if (a.rfind("--", 0) == 0) { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
         else pos.push_back(a);
     }
     if (pos.empty()) {
         std::fprintf(stderr, "usage: %s model.obj [grid] [width] [height] [frames] [out.ppm] [devices] "
-                             "[--model=reference|identity] [--grid=fit|unit]\n", argv[0]);
+                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32]\n",
+                     argv[0]);
         return 2;
     }
     ConeTraceSettings s;
@@ -45,6 +54,8 @@ int main(int argc, char** argv) {
     const std::string out = pos.size() > 5 ? pos[5] : "vct_frame.ppm";
     if (pos.size() > 6) s.devices = (uint32_t)std::atoi(pos[6].c_str());
     if (s.grid < 4) { std::fprintf(stderr, "grid must be >= 4\n"); return 2; }
+    if (bounces < 0) { std::fprintf(stderr, "--bounces must be >= 0\n"); return 2; }
+    s.bounces = (uint32_t)bounces;
     if (ref_model) ReferenceModelMatrix(s.model);
 
     AssetsManager& A = AssetsManager::Instance();            // assets.cpp:22-45
@@ -79,6 +90,7 @@ int main(int argc, char** argv) {
                     r->last_cone_steps(), r->last_cone_steps() / (r->last_trace_ms() * 1e3));
     }
     if (!r->WritePPM(out)) return 1;
+    if (!linear.empty() && !r->WriteLinear(linear)) return 1;
     std::printf("wrote %s\n", out.c_str());
     return 0;
 }

@@ -68,6 +68,7 @@ bool ConeTraceRenderer::rebuild_scene() {
         return false;
     if (!check(vct_inject_directional(ctx_, s_.light_dir, s_.light_color), "vct_inject_directional")) return false;
     if (!check(vct_build_mips(ctx_), "vct_build_mips")) return false;
+    if (s_.bounces && !check(vct_inject_bounces(ctx_, s_.bounces), "vct_inject_bounces")) return false;
     scene_dirty_ = false;
     return true;
 }
@@ -129,6 +130,25 @@ bool ConeTraceRenderer::WritePPM(const std::string& path) {
     }
     std::fclose(f);
     return true;
+}
+
+bool ConeTraceRenderer::WriteLinear(const std::string& path) {
+    if (!ctx_) return false;
+    const size_t px = (size_t)s_.width * s_.height;
+    void* lin = nullptr;
+    if (!check(vct_device_alloc(ctx_, px * 16, &lin), "alloc linear frame")) return false;
+    std::vector<float> img(px * 4);
+    const bool ok = check(vct_composite_device(ctx_, (const float*)gb_[0], (const float*)gb_[1], (const float*)gb_[2],
+                                               (const float*)out_[0], (const float*)out_[1], s_.width, s_.height,
+                                               s_.light_dir, s_.light_color, (float*)lin, nullptr),
+                          "vct_composite_device") &&
+                    check(vct_memcpy(ctx_, img.data(), lin, px * 16, 1), "download linear frame");
+    vct_device_free(ctx_, lin);
+    if (!ok) return false;
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    const bool wrote = std::fwrite(img.data(), sizeof(float), img.size(), f) == img.size();
+    return std::fclose(f) == 0 && wrote;
 }
 
 }  // namespace vcthost

@@ -5,7 +5,7 @@
 // `ConeTraceRenderer` is the drop-in that replaces the forward GL draw of
 // VoxelizationRenderer::Render (r_voxelization.cpp:4-35) with the C-ABI of
 // include/vct.h: on the first frame (or when the scene/light changes) it runs
-// K1 voxelize -> K2 inject -> K3 mips, and every frame it builds the G-buffer
+// K1 voxelize -> K2 inject -> K3 mips (-> `bounces` light bounces), and every frame it builds the G-buffer
 // from the active camera and runs K4.  State is pulled from the registry the
 // way the reference pulls programs/models/camera from its singletons.
 #pragma once
@@ -34,6 +34,8 @@ struct ConeTraceSettings {
     float aabb_min[3] = {-1.0f, -1.0f, -1.0f};
     float extent = 2.0f;
     uint32_t devices = 1;                 // > 1: one context over that many GPUs (vct_create_multi)
+    uint32_t bounces = 0;                 // light bounces added to the grid after each inject + build
+                                          // (vct_inject_bounces; 0: direct light only)
     // model matrix applied to the model's vertices before K1, column-major; main.cpp
     // sets the reference's T(0,-1.75,0) S(0.2) (r_voxelization.cpp:26-29) by default
     float model[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
@@ -52,6 +54,8 @@ public:
     unsigned long long last_cone_steps() const { return last_steps_; }
     // composite + present (vct_composite_device: direct + albedo * indirect + specular) -> binary PPM
     bool WritePPM(const std::string& path);
+    // the same composite before tone mapping: width x height x 4 float32, row 0 = top, raw little-endian
+    bool WriteLinear(const std::string& path);
 
 private:
     bool check(vct_status s, const char* what);

@@ -252,6 +252,19 @@ class Context:
     def build_mips(self):
         self._check(self.lib.vct_build_mips(self.h), "build_mips")
 
+    def inject_bounces(self, n_bounces: int = 1):
+        """vct_inject_bounces: n more light bounces into level 0 (after inject + build_mips;
+        the mips are rebuilt).  Once per level 0: VctError(ESTATE) on a second call."""
+        fn = _lib.bind_extension(self.lib, "vct_inject_bounces")
+        self._check(fn(self.h, int(n_bounces)), "inject_bounces")
+
+    def bounce_sources(self) -> int:
+        """vct_bounce_sources: occupied voxels with a nonzero normal (the bounce's cone origins)."""
+        fn = _lib.bind_extension(self.lib, "vct_bounce_sources")
+        n = C.c_uint32()
+        self._check(fn(self.h, C.byref(n)), "bounce_sources")
+        return int(n.value)
+
     # -- K4 ---------------------------------------------------------------
     def trace(self, pos4: np.ndarray, nrm4: np.ndarray, alb4: np.ndarray, eye, want_steps=True):
         h, w = pos4.shape[:2]

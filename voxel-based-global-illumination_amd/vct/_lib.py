@@ -29,6 +29,11 @@ EXPORTS = (
     "vct_save_grid", "vct_load_grid", "vct_dump_info",
 )
 
+# include/vct_bounce.h: the additive part of the boundary that only the HIP library
+# implements.  Bound on first use (bind_extension), so that a library without these
+# symbols -- the CPU oracle backend -- still loads and binds.
+EXTENSIONS = ("vct_inject_bounces", "vct_bounce_sources")
+
 STATUS = {0: "VCT_OK", 1: "VCT_EINVAL", 2: "VCT_ENOMEM", 3: "VCT_EDEVICE", 4: "VCT_ECOMM", 5: "VCT_ESTATE"}
 
 
@@ -173,3 +178,22 @@ def bind(lib: C.CDLL) -> C.CDLL:
         fn.restype = res
         fn.argtypes = args
     return lib
+
+
+def bind_extension(lib: C.CDLL, name: str):
+    """The include/vct_bounce.h function `name` of `lib`, with its signature declared;
+    AttributeError (naming the library) if this implementation does not export it."""
+    P, u32, i32 = C.c_void_p, C.c_uint32, C.c_int32
+    sig = {
+        "vct_inject_bounces": (i32, [P, u32]),
+        "vct_bounce_sources": (i32, [P, C.POINTER(u32)]),
+    }
+    res, args = sig[name]
+    try:
+        fn = getattr(lib, name)
+    except AttributeError:
+        raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
+                             "(include/vct_bounce.h is implemented by the HIP library only)") from None
+    fn.restype = res
+    fn.argtypes = args
+    return fn
