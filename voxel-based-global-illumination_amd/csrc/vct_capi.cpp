@@ -223,6 +223,13 @@ vct_status vct_create(const vct_config* cfg, vct_ctx** out) {
             g.zm_off[m] = zw;
             zw += g.zm_dim[m] * g.zm_dim[m] * g.zm_rw[m];
         }
+        if (g.n <= Grid::kZMap0MaxN) {       // map 0 goes last: the offsets of maps 1.. do not depend on it
+            g.zm_dim[0] = g.n + 1u;
+            g.zm_rw[0] = (g.zm_dim[0] + 31u) / 32u;
+            g.zm_off[0] = zw;
+            zw += g.zm_dim[0] * g.zm_dim[0] * g.zm_rw[0];
+        }
+        g.zm_words = zw;
         e = hipMalloc((void**)&g.b0, nv / 8);
         if (e == hipSuccess) e = hipMalloc((void**)&g.occ, ob ? ob : 1);
         if (e == hipSuccess) e = hipMalloc((void**)&g.zmap, (size_t)zw * 4);

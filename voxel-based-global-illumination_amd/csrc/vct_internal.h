@@ -34,20 +34,27 @@ struct Grid {
     // K4 empty-space maps (vct_mips.hip, rebuilt by every build_mips): b0 = one bit per
     // level-0 texel, set iff the texel is not +0 (bit order = the texel's index in the brick
     // layout, so byte v = the eight children of level-1 texel v); occ = per level m >= 2 one
-    // byte per texel, nonzero iff some level-0 texel under it is; zmap = per level m = 1..zm_levels
+    // byte per texel, nonzero iff some level-0 texel under it is; zmap = per level m = 0..zm_levels
     // one bit per position p in [-1, n_m - 1]^3 (stored at p + 1), set iff any level-m texel of
-    // p + {0,1}^3 may be nonzero.  A level-l trilinear footprint at corner c lies under the
-    // level-(l+1) texels c >> 1 + {0,1}^3, so a clear bit of map l+1 at c >> 1 proves the
-    // footprint's texels (every face) are +0.
+    // p + {0,1}^3 may be nonzero (texels outside the level are zero).  A level-l trilinear
+    // footprint at corner c is exactly the texels c + {0,1}^3, so a clear bit of map l at c
+    // proves the footprint's texels (every face) are +0 (zm_sh = 0, the exact test).  It also
+    // lies under the level-(l+1) texels c >> 1 + {0,1}^3, so a clear bit of map l+1 at c >> 1
+    // proves the same for the 4^3 aligned region around it (zm_sh = 1, the coarse test).
+    // Map 0 (from b0; 2.3 MB at 256^3, 18 MB at 512^3) is only kept for n <= kZMap0MaxN:
+    // above that, level 0 keeps the coarse test whatever zm_sh says.
     static constexpr int kZLevels = 5;
+    static constexpr uint32_t kZMap0MaxN = 512;
     uint32_t* b0 = nullptr;                  // [n^3 / 32]
     uint8_t* occ = nullptr;                  // levels 2..zm_levels, byte per texel, back to back
     uint64_t occ_off[kZLevels + 1] = {};     // byte offset of level m in occ (m >= 2)
-    uint32_t* zmap = nullptr;                // maps 1..zm_levels, back to back
+    uint32_t* zmap = nullptr;                // maps 1..zm_levels back to back, then map 0
     uint32_t zm_off[kZLevels + 1] = {};      // dword offset of map m
-    uint32_t zm_dim[kZLevels + 1] = {};      // n_m + 1 positions per axis
+    uint32_t zm_dim[kZLevels + 1] = {};      // n_m + 1 positions per axis (zm_dim[0] = 0: no map 0)
     uint32_t zm_rw[kZLevels + 1] = {};       // dwords per row of map m
+    uint32_t zm_words = 0;                   // dwords of zmap
     int zm_levels = 0;
+    int zm_sh = 0;                           // 0: exact test, 1: coarse (VCT_ZMAP_EXACT=0), set by build_mips
     bool zm_valid = false;                   // the maps describe the current pyramid
     // Relight builds (vct_mips.hip launch_mips): after K2, level 0 is nonzero exactly at
     // the occupied voxels (every one gets alpha 1, every other voxel is +0), a pattern only

@@ -375,6 +375,43 @@ __device__ __forceinline__ uint32_t zbits_word(const uint8_t* __restrict__ bytes
     return bits;
 }
 
+// map 0: the same dword from Grid::b0, whose byte v holds the eight level-0 children of
+// level-1 texel v (bit dx + 2 dy + 4 dz).  A texel row (y, z) is the bit pair 2 (y & 1) +
+// 4 (z & 1) of the bytes of level-1 row (y >> 1, z >> 1): a dword of b0 gives eight texels.
+__device__ __forceinline__ uint32_t zbits0_word(const uint8_t* __restrict__ b0, uint32_t n, uint32_t wx,
+                                                uint32_t py, uint32_t pz) {
+    const uint32_t n1 = n >> 1;
+    const int d0 = (int)(wx * 4u), nd = (int)(n1 >> 2);   // dword d of a row: texels 8 d .. 8 d + 7 (n1 is a multiple of 8)
+    uint32_t bits = 0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int y = (int)py - 1 + (r & 1), z = (int)pz - 1 + (r >> 1);
+        if (y < 0 || z < 0 || y >= (int)n || z >= (int)n) continue;
+        const uint32_t* row =
+            reinterpret_cast<const uint32_t*>(b0 + ((size_t)(z >> 1) * n1 + (size_t)(y >> 1)) * n1);
+        const uint32_t sh = 2u * ((uint32_t)y & 1u) + 4u * ((uint32_t)z & 1u);
+        unsigned long long t = 0;                    // bit b: texel 32 wx - 1 + b is not +0
+#pragma unroll
+        for (int q = -1; q < 4; ++q) {
+            const int d = d0 + q;
+            if (d < 0 || d >= nd) continue;
+            const uint32_t p = (row[d] >> sh) & 0x03030303u;
+            const uint32_t e = (p & 3u) | ((p >> 6) & 0xcu) | ((p >> 12) & 0x30u) | ((p >> 18) & 0xc0u);
+            if (q < 0) t |= e >> 7;
+            else t |= (unsigned long long)e << (8 * q + 1);
+        }
+        bits |= (uint32_t)(t | (t >> 1));
+    }
+    return bits;
+}
+
+__global__ void __launch_bounds__(256) k_zbits0(const uint8_t* __restrict__ b0, uint32_t n, uint32_t* __restrict__ dst,
+                                                uint32_t dim, uint32_t rw) {
+    const size_t wi = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (wi >= (size_t)dim * dim * rw) return;
+    dst[wi] = zbits0_word(b0, n, (uint32_t)(wi % rw), (uint32_t)((wi / rw) % dim), (uint32_t)(wi / ((size_t)rw * dim)));
+}
+
 __global__ void __launch_bounds__(256) k_zbits(const uint8_t* __restrict__ bytes, uint32_t nm,
                                                uint32_t* __restrict__ dst, uint32_t dim, uint32_t rw) {
     const size_t wi = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -389,6 +426,7 @@ struct ZMapsK {
     int levels;
     uint32_t end[Grid::kZLevels + 1];       // exclusive end dword of map m (maps back to back)
     uint32_t dim[Grid::kZLevels + 1], rw[Grid::kZLevels + 1], occ_off[Grid::kZLevels + 1];
+    uint32_t end0;                          // map 0 follows map `levels` (dim[0], rw[0]; end0 = end[levels]: none)
 };
 
 // Occupancy bytes of levels 2 .. 5 in one launch: a 256-thread workgroup owns a 16^3
@@ -443,7 +481,12 @@ __global__ void __launch_bounds__(256) k_zbits_all(const uint8_t* __restrict__ b
     const uint32_t wi = blockIdx.x * blockDim.x + threadIdx.x;
     int m = 1;
     while (m < z.levels && wi >= z.end[m]) ++m;
-    if (wi >= z.end[m]) return;
+    if (wi >= z.end[m]) {
+        if (wi >= z.end0) return;
+        const uint32_t dim = z.dim[0], rw = z.rw[0], li = wi - z.end[m];
+        dst[wi] = zbits0_word(b0, dim - 1u, li % rw, (li / rw) % dim, li / (rw * dim));
+        return;
+    }
     const uint32_t first = m == 1 ? 0u : z.end[m - 1];
     const uint8_t* bytes = m == 1 ? b0 : occ + z.occ_off[m];
     const uint32_t dim = z.dim[m], rw = z.rw[m], nm = dim - 1u, li = wi - first;
@@ -470,6 +513,9 @@ hipError_t launch_zmaps(vct_ctx* c, hipStream_t st) {
             z.rw[m] = g.zm_rw[m];
             z.occ_off[m] = (uint32_t)g.occ_off[m];
         }
+        z.dim[0] = g.zm_dim[0];
+        z.rw[0] = g.zm_rw[0];
+        z.end0 = end += g.zm_dim[0] * g.zm_dim[0] * g.zm_rw[0];   // zm_off[0] = end[levels] (vct_create)
         hipLaunchKernelGGL(k_zbits_all, dim3((end + 255) / 256), dim3(256), 0, st, (const uint8_t*)g.b0,
                            (const uint8_t*)g.occ, z, g.zmap);
         return hipGetLastError();
@@ -487,6 +533,11 @@ hipError_t launch_zmaps(vct_ctx* c, hipStream_t st) {
         hipLaunchKernelGGL(k_zbits, dim3((uint32_t)((words + 255) / 256)), dim3(256), 0, st,
                            m == 1 ? (const uint8_t*)g.b0 : g.occ + g.occ_off[m], g.n >> m, g.zmap + g.zm_off[m],
                            g.zm_dim[m], g.zm_rw[m]);
+    }
+    if (g.zm_dim[0]) {
+        const size_t words = (size_t)g.zm_dim[0] * g.zm_dim[0] * g.zm_rw[0];
+        hipLaunchKernelGGL(k_zbits0, dim3((uint32_t)((words + 255) / 256)), dim3(256), 0, st, (const uint8_t*)g.b0,
+                           g.n, g.zmap + g.zm_off[0], g.zm_dim[0], g.zm_rw[0]);
     }
     return hipGetLastError();
 }
@@ -533,7 +584,7 @@ __global__ void __launch_bounds__(256) k3_live_compact(const uint8_t* __restrict
 // 512^3, and 8 x 8 x 2 by 3-4 %: twice the workgroups in flight per CU hide the staging
 // loads better than the one saved launch (relight builds too: tools/k3_shapes.sh).
 // VCT_K3_BZ = 8 | 2 selects the others (A/B).
-// The K3 A/B switches (VCT_K3_BZ, VCT_K3_PLAN, VCT_K3_WRITE, VCT_K3_SPARSE, VCT_ZMAP) are
+// The K3 A/B switches (VCT_K3_BZ, VCT_K3_PLAN, VCT_K3_WRITE, VCT_K3_SPARSE, VCT_ZMAP, VCT_ZMAP_EXACT) are
 // all read per call, so a process can flip one between builds and see exactly that one
 // change (a getenv per build is nothing beside the build).  They interact in one place:
 // VCT_ZMAP=0 leaves the K4 maps invalid, and a relight-sparse build needs the maps of the
@@ -579,6 +630,7 @@ hipError_t launch_mips(vct_ctx* c) {
     g.zm_valid = false;
     const char* plan = getenv("VCT_K3_PLAN");   // A/B switches: read per call (k3_block_depth)
     const bool zmap_on = !env_off("VCT_ZMAP");
+    g.zm_sh = env_off("VCT_ZMAP_EXACT") ? 1 : 0;   // A/B: the coarse test (map l+1 at c >> 1); both read the same maps
     if (plan && strcmp(plan, "level") == 0) {                            // A/B: one lane-per-parent launch per level (no K4 maps)
         for (uint32_t l = 1; l <= g.L; ++l) {
             const int nl = (int)(g.n >> l);

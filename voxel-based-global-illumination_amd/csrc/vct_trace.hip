@@ -172,9 +172,11 @@ struct TraceK {
     uint32_t npx;                // its length (w * h)
     const uint32_t* order;       // dispatch order: workgroup i traces unit order[i] (null: unit i)
     uint32_t* dur;               // per unit: its wave's duration in s_memrealtime ticks (null: not recorded)
-    const uint32_t* zmap;        // Grid::zmap (empty-space maps 1..zm_levels; zm_levels = 0: no test)
+    const uint32_t* zmap;        // Grid::zmap (empty-space maps zm_lo..zm_levels; zm_levels = -1: no test)
     uint32_t zmap_bytes;
     int zm_levels;
+    int zm_sh;                   // 0: level l tests map l at its corner (exact), 1: map l+1 at corner >> 1
+    int zm_lo;                   // the lowest map (1: no map 0, level 0 tests map 1)
     ZLevel zm[Grid::kZLevels + 1];
 };
 
@@ -566,15 +568,24 @@ __device__ __forceinline__ bool in_brick(const Corner& c, const BrickEntry& b, i
     return max(max((uint32_t)(c.ix - b.ox), (uint32_t)(c.iy - b.oy)), (uint32_t)(c.iz - b.oz) << z3) <= 2u;
 }
 
-// Empty-space test of one lane's level-l trilinear footprint (corner c): its texels lie
-// under the level-(l+1) texels (c >> 1) + {0,1}^3, so bit (c >> 1) of map l+1 clear means
-// every one of them, in every face, is +0 -- the sample is exactly +0 (the trilinear
-// fmaf chain of zeros), the same value the texels would give.  1 when there is no map.
+// Experiment build (make exp NAME=lvlb EXP=-DVCT_ZMAP_LEVELB=1): a level-B miss takes the
+// same empty-space test before it restages or gathers.  Not shipped: DESIGN §12.2.
+#ifndef VCT_ZMAP_LEVELB
+#define VCT_ZMAP_LEVELB 0
+#endif
+
+// Empty-space test of one lane's level-l trilinear footprint (corner c): its texels are
+// c + {0,1}^3, which is what bit c of map l covers (sh = 0); they also lie under the
+// level-(l+1) texels (c >> 1) + {0,1}^3, bit c >> 1 of map l+1 (sh = 1: a 4^3 region of
+// level l, nonempty far more often).  A clear bit means every one of them, in every face,
+// is +0 -- the sample is exactly +0 (the trilinear fmaf chain of zeros), the same value
+// the texels would give.  1 when there is no map.  sh is wave-uniform (scalar).
 __device__ __forceinline__ uint32_t zbit(const TraceK& k, int l, const Corner& c) {
-    const int m = l + 1;
+    const int sh = l < k.zm_lo ? 1 : k.zm_sh;
+    const int m = l + sh;
     if (m > k.zm_levels) return 1u;
     const ZLevel z = k.zm[m];
-    const uint32_t X = (uint32_t)((c.ix >> 1) + 1), Y = (uint32_t)((c.iy >> 1) + 1), Z = (uint32_t)((c.iz >> 1) + 1);
+    const uint32_t X = (uint32_t)((c.ix >> sh) + 1), Y = (uint32_t)((c.iy >> sh) + 1), Z = (uint32_t)((c.iz >> sh) + 1);
     // an inactive lane's corner may be garbage: its offset reads 0 past the range (and
     // its bit is masked off by the caller)
     const uint32_t w = z.off + __umul24(__umul24(Z, z.dim) + Y, z.rw) + (X >> 5);
@@ -844,15 +855,22 @@ __device__ __forceinline__ float4 step_bricks(const TraceK& k, int l0, float qx,
     // a level-A miss first tests for empty space (Grid::zmap): nzA = the active lanes whose
     // footprint may hold a nonzero texel; none -> the sample is exactly +0 and neither a
     // staging nor a gather happens.  Measured (atrium / courtyard, A/B in one box): -2.6 % /
-    // -4.5 %.  Not kept: the same test for level B (its misses are mostly nonempty
-    // stagings, which then wait for two round trips: +2 % / +1 %), before level B's gathers
+    // -4.5 % with the coarse test (zm_sh = 1); the exact test (zm_sh = 0, map l at the
+    // footprint's own corner) a further -8.4 % / -8.2 %.
+    // Not kept: the same test for level B (VCT_ZMAP_LEVELB; its misses are mostly nonempty
+    // stagings, which then wait for two round trips: +2 % / +1 % with the coarse maps,
+    // +3.9 % / +4.0 % with the exact ones), before level B's gathers
     // only (+3 %), only on level A's gather path (+1 %), only for levels <= 1 or <= 2 (the
     // gain shrinks), maps up to level 5 instead of 4 (+0.5 %), and the bit of the next
     // step's level A loaded one step ahead (its position and corner VALU: +7 %).
     // level B restages first: its loads go out before level A's empty-space test waits, so
     // the two round trips overlap (A/B: atrium -1.0 %, courtyard -0.3 %)
+    bool emptyB = false;
+#if VCT_ZMAP_LEVELB
+    if (needB && !useB) emptyB = (wballot(zbit(k, l1, cB) != 0u) & amB) == 0ull;
+#endif
     bool stB = false;
-    if (needB && !useB && (modeB != kFaces || faces_okB)) {
+    if (needB && !useB && !emptyB && (modeB != kFaces || faces_okB)) {
         BrickEntry nb{};
         nb.lvl = l1;
         if (brick_origin(cB, amB, cc.neg, nb, z3B)) {
@@ -927,7 +945,7 @@ __device__ __forceinline__ float4 step_bricks(const TraceK& k, int l0, float qx,
         if (__builtin_amdgcn_inverse_ballot_w64(nzA))
             sA = sample_level<O32, true, gather_chunk<UNION>()>(k, l0, qx, qy, qz, ld.fx(), ld.fy(), ld.fz(), ld.wx(), ld.wy(), ld.wz());
     }
-    if (needB && !useB) {
+    if (needB && !useB && !emptyB) {
         VCT_DBG(4 + (l1 < 10 ? l1 : 10));
         dbg_fallback_reason(cB, activeB, modeB != kFaces || faces_okB, l1, AM == kComb || modeB != kFaces);
         if (activeB)
@@ -1766,12 +1784,11 @@ hipError_t launch_trace(vct_ctx* c, const vct_trace_args* a, int bounce_form) {
     k.dur = bounce ? nullptr : c->k4_dbg_dur;
     k.npx = a->width * a->height;
     k.zmap = g.zm_valid ? g.zmap : nullptr;
-    k.zm_levels = g.zm_valid ? g.zm_levels : 0;
-    k.zmap_bytes = 0;
-    for (int m = 0; m <= Grid::kZLevels; ++m) {
-        k.zm[m] = ZLevel{g.zm_off[m], g.zm_dim[m], g.zm_rw[m], 0u};
-        if (m >= 1 && m <= k.zm_levels) k.zmap_bytes = 4u * (g.zm_off[m] + g.zm_dim[m] * g.zm_dim[m] * g.zm_rw[m]);
-    }
+    k.zm_levels = g.zm_valid ? g.zm_levels : -1;
+    k.zm_sh = g.zm_sh;
+    k.zm_lo = g.zm_dim[0] ? 0 : 1;
+    k.zmap_bytes = k.zmap ? 4u * g.zm_words : 0u;
+    for (int m = 0; m <= Grid::kZLevels; ++m) k.zm[m] = ZLevel{g.zm_off[m], g.zm_dim[m], g.zm_rw[m], 0u};
     // low byte: 0 default, 1 per-lane gathers; the other variant bits of vct_variants.h
     if ((a->variant & 0xfe) != 0 || (a->variant & kVarRetired) != 0) return hipErrorInvalidValue;
     uint32_t nlt = tiles_for_rank(a->width, a->height, (uint32_t)k.rank, world);
@@ -1952,6 +1969,23 @@ extern "C" int vct_debug_k4_sched(vct_ctx* c, const uint32_t* order, uint32_t* d
 
 // Test hook: the number of K4 launches of this context dispatched in a longest-first order.
 extern "C" long long vct_debug_k4_lpt_launches(const vct_ctx* c) { return c ? (long long)c->k4_lpt_launches : -1; }
+
+// Test hook: copies empty-space map m (Grid::zmap) of the last build_mips to the host and
+// reports its shape (dim positions per axis, rows of rw dwords).  Returns the map's dwords,
+// or -1 (no such map, maps not current, out too small, or a HIP error).
+extern "C" long long vct_debug_zmap(vct_ctx* c, int m, uint32_t* out, size_t cap_dwords, uint32_t* dim, uint32_t* rw) {
+    if (!c || !out || m < 0) return -1;
+    const vct::Grid& g = c->grid;
+    // (a level-0 write clears `mipped`, not zm_valid: the trace is refused until the next build)
+    if (!g.mipped || !g.zm_valid || m > g.zm_levels || g.zm_dim[m] == 0) return -1;
+    const size_t words = (size_t)g.zm_dim[m] * g.zm_dim[m] * g.zm_rw[m];
+    if (cap_dwords < words || hipSetDevice(c->device) != hipSuccess) return -1;
+    if (hipMemcpyAsync(out, g.zmap + g.zm_off[m], words * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return -1;
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return -1;
+    if (dim) *dim = g.zm_dim[m];
+    if (rw) *rw = g.zm_rw[m];
+    return (long long)words;
+}
 
 #if defined(VCT_DEBUG_CLOCK) || defined(VCT_DEBUG_WAVES)
 extern "C" int vct_debug_waves(unsigned long long* out, int n) {   // out[n][3]; n <= 1 << 18

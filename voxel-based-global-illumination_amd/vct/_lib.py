@@ -197,3 +197,23 @@ def bind_extension(lib: C.CDLL, name: str):
     fn.restype = res
     fn.argtypes = args
     return fn
+
+
+def debug_zmap(lib: C.CDLL, handle, m: int):
+    """Test hook (vct_debug_zmap, not part of include/vct.h): K4's empty-space map m of the
+    last build_mips as a uint32 array [dim, dim, rw] (z, y, row dwords), or None when the
+    context has no such map or its maps are not current."""
+    import numpy as np
+    fn = lib.vct_debug_zmap
+    fn.restype = C.c_longlong
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    cfg = VctConfig()
+    if lib.vct_get_config(handle, C.byref(cfg)) != 0:
+        return None
+    dim_max = cfg.n + 1
+    out = np.zeros(dim_max * dim_max * ((dim_max + 31) // 32), np.uint32)
+    dim, rw = C.c_uint32(), C.c_uint32()
+    words = fn(handle, m, out.ctypes.data, out.size, C.byref(dim), C.byref(rw))
+    if words < 0:
+        return None
+    return out[:words].reshape(dim.value, dim.value, rw.value).copy()
