@@ -401,5 +401,7 @@ vct_status vct_dump_info(const char* stem, vct_config* cfg, uint32_t* what);
 
 /* ---- light bounces (additive; HIP library only) ---------------------------------- */
 #include "vct_bounce.h"
+/* ---- point and spot lights (additive; HIP library only) -------------------------- */
+#include "vct_lights.h"
 
 #endif /* VCT_H */

@@ -170,4 +170,45 @@
  *    exactly at the occupied voxels (alpha), so the relight mip build stays legal.
  *  n_diffuse = 0: I = 0 and L stays L0. */
 
+/* ---- local lights (vct_inject_lights / vct_composite_lights_device, include/vct_lights.h;
+ *      no new literals) ------------------------------------------------------------------
+ * No fused operation: every step below is one IEEE float op, in the order written; sqrtf
+ * and / are correctly rounded, denormals are kept.
+ *      dot3(a, b) = (ax*bx + ay*by) + az*bz
+ *      inv_h = (float)n / E,  hh = E / (float)n                    (float divides)
+ *  Per light, once, on the host:
+ *    directional:  l = d / sqrtf(dot3(d, d)) per component, as vct_inject_directional
+ *    point, spot:  pL_c   = (position_c - g0_c) * inv_h            (voxel units)
+ *                  rv     = range * inv_h
+ *                  inv_rr = 1.0f / (rv * rv)
+ *                  h2     = hh * hh
+ *    spot only:    a        = -(direction / sqrtf(dot3(direction, direction)))
+ *                  inv_span = 1.0f / (cos_inner - cos_outer)
+ *  Per receiver and per light, in list order.  A receiver is, in K2, an occupied voxel
+ *  (x, y, z) with resolved normal N and albedo A, q_c = ((float)x_c + 0.5f) + N_c; in the
+ *  composite, a pixel with position P, normal N, albedo A, q_c = (P_c - g0_c) * inv_h + N_c.
+ *    directional:  l = the light's l,  f = 1.0f,  t_lim = +inf
+ *    point, spot:  d = pL - q,  r2 = dot3(d, d);  the light is skipped unless r2 > 0
+ *                  r = sqrtf(r2),  l_c = d_c / r,  t_lim = r
+ *                  u = r2 * inv_rr,  w = fmaxf(1.0f - u, 0.0f)
+ *                  f = (w * w) / (1.0f + r2 * h2)
+ *    spot only:    cd = dot3(l, a)
+ *                  s = fminf(fmaxf((cd - cos_outer) * inv_span, 0.0f), 1.0f)
+ *                  f = f * (s * s)
+ *    ndl = dot3(N, l);  the light is skipped unless ndl > 0 and f > 0.
+ *  (f is the physical 1 / (1 + r_world^2) falloff under a window that reaches zero, with a
+ *  zero slope, at r_world = range.)
+ *  Visibility V: the A.3 shadow walk (vct_device.h dda_visibility) from q along l, cell
+ *  for cell, with one more end.  t_e is the t at which the current cell was entered: 0 for
+ *  the first cell; after a step, the tm value that was the minimum chosen (before td is
+ *  added to it).  Before a cell is tested: t_e >= t_lim gives V = 1 (the light is
+ *  reached).  A start cell outside the grid gives V = 1 as in A.3.
+ *  Sum:  contrib_c = (((A_c * color_c) * ndl) * f) * V
+ *        acc = +0;  acc_c = acc_c + contrib_c  for the lights not skipped, in list order
+ *    K2 writes (acc, 1) at the voxel; the composite uses direct = acc in
+ *    final = (direct + A * D) + S.
+ *  One directional light therefore reproduces vct_inject_directional and
+ *  vct_composite_device bit for bit (x * 1.0f and +0 + x are exact for x >= 0), and the
+ *  order of the list is part of the result. */
+
 #endif /* VCT_SPEC_H */

@@ -186,7 +186,9 @@ void ConeTraceRenderer::Render()
 	if (light_dirty_)
 	{
 		// a relit frame: K2 + K3 only (a relight build keeps K1's occupancy work)
-		if (!Check(vct_inject_directional(ctx_, light_dir_, light_color_), "vct_inject_directional") ||
+		if (!Check(lights.empty() ? vct_inject_directional(ctx_, light_dir_, light_color_)
+		                          : vct_inject_lights(ctx_, lights.data(), (uint32_t)lights.size()),
+		           lights.empty() ? "vct_inject_directional" : "vct_inject_lights") ||
 		    !Check(vct_build_mips(ctx_), "vct_build_mips"))
 			return;
 		if (bounces && !Check(vct_inject_bounces(ctx_, bounces), "vct_inject_bounces")) return;
@@ -222,9 +224,12 @@ void ConeTraceRenderer::Render()
 	if (!Check(vct_trace_device(ctx_, &a), "vct_trace_device")) return;
 	// direct + albedo x indirect + specular, tone-mapped to RGBA8 on the GPU (background =
 	// r_voxelization.cpp:8's clear colour), then one copy to the host for GL
-	if (!Check(vct_composite_device(ctx_, a.pos4, a.nrm4, a.alb4, a.diffuse4, a.spec4, width_, height_, light_dir_,
-	                                light_color_, nullptr, (uint32_t*)rgba_),
-	           "vct_composite_device") ||
+	const vct_status composed =
+	    lights.empty() ? vct_composite_device(ctx_, a.pos4, a.nrm4, a.alb4, a.diffuse4, a.spec4, width_, height_,
+	                                          light_dir_, light_color_, nullptr, (uint32_t*)rgba_)
+	                   : vct_composite_lights_device(ctx_, a.pos4, a.nrm4, a.alb4, a.diffuse4, a.spec4, width_, height_,
+	                                                 lights.data(), (uint32_t)lights.size(), nullptr, (uint32_t*)rgba_);
+	if (!Check(composed, lights.empty() ? "vct_composite_device" : "vct_composite_lights_device") ||
 	    !Check(vct_memcpy(ctx_, pixels_.data(), rgba_, pixels_.size() * 4, 1), "download RGBA8"))
 		return;
 	Present();

@@ -34,6 +34,12 @@ public:
 	// 0: the grid holds direct light only).  Takes effect with the next relight.
 	unsigned bounces = 0;
 
+	// a light list (include/vct_lights.h: directional, point and spot lights, summed in list
+	// order).  When non-empty it replaces the directional light of SetLight in K2 and in the
+	// composite; call SetLights so that the next frame relights.
+	std::vector<vct_light> lights;
+	void SetLights(const std::vector<vct_light>& list) { lights = list; light_dirty_ = true; }
+
 	bool Ok() const { return ok_; }
 
 private:

@@ -5,6 +5,7 @@
 //
 //   vct_headless <model.obj> [grid=256] [width=800] [height=600] [frames=5] [out.ppm] [devices=1]
 //                [--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32]
+//                [--light SPEC]...
 //   (devices > 1: one process drives that many GPUs through vct_create_multi)
 //   --model: the model matrix of the reference's draw, T(0,-1.75,0) S(0.2)
 //            (r_voxelization.cpp:26-29; default), or none;
@@ -13,6 +14,14 @@
 //   --bounces: light bounces added to the grid after each inject + build
 //            (vct_inject_bounces; default 0);
 //   --linear: also dump the last frame before tone mapping (raw float32 [h][w][4]).
+//   --light:  one light of a light list (include/vct_lights.h), repeatable, in list order; with
+//            any --light the list replaces the default directional light.  SPEC is colon-
+//            separated fields of comma-separated floats, world units, angles in degrees:
+//              dir:dx,dy,dz:r,g,b                     (direction toward the light)
+//              point:x,y,z:r,g,b:range
+//              spot:x,y,z:dx,dy,dz:r,g,b:range:inner_deg:outer_deg   (d = the axis it shines along)
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <memory>
@@ -23,11 +32,60 @@
 
 using namespace vcthost;
 
+// one --light SPEC (see above) -> *out; false: malformed
+static bool parse_light(const std::string& spec, vct_light* out) {
+    std::vector<std::vector<float>> f;      // the numeric fields after the type
+    std::string type;
+    size_t at = 0;
+    for (int k = 0; at <= spec.size(); ++k) {
+        const size_t end = std::min(spec.find(':', at), spec.size());
+        const std::string field = spec.substr(at, end - at);
+        at = end + 1;
+        if (k == 0) { type = field; continue; }
+        std::vector<float> v;
+        const char* p = field.c_str();
+        while (*p) {
+            char* q = nullptr;
+            v.push_back(std::strtof(p, &q));
+            if (q == p) return false;
+            p = *q == ',' ? q + 1 : q;
+            if (*q && *q != ',') return false;
+        }
+        f.push_back(v);
+    }
+    auto is = [&](size_t i, size_t n) { return i < f.size() && f[i].size() == n; };
+    auto put3 = [](float* dst, const std::vector<float>& v) { for (int k = 0; k < 3; ++k) dst[k] = v[k]; };
+    *out = vct_light{};
+    if (type == "dir" && f.size() == 2 && is(0, 3) && is(1, 3)) {
+        out->type = VCT_LIGHT_DIRECTIONAL;
+        put3(out->direction, f[0]);
+        put3(out->color, f[1]);
+    } else if (type == "point" && f.size() == 3 && is(0, 3) && is(1, 3) && is(2, 1)) {
+        out->type = VCT_LIGHT_POINT;
+        put3(out->position, f[0]);
+        put3(out->color, f[1]);
+        out->range = f[2][0];
+    } else if (type == "spot" && f.size() == 6 && is(0, 3) && is(1, 3) && is(2, 3) && is(3, 1) && is(4, 1) && is(5, 1)) {
+        out->type = VCT_LIGHT_SPOT;
+        put3(out->position, f[0]);
+        put3(out->direction, f[1]);
+        put3(out->color, f[2]);
+        out->range = f[3][0];
+        const float rad = 3.14159265358979323846f / 180.0f;
+        out->cos_inner = std::cos(f[4][0] * rad);
+        out->cos_outer = std::cos(f[5][0] * rad);
+    } else {
+        return false;
+    }
+    return true;
+}
+
 int main(int argc, char** argv) {
     std::vector<std::string> pos;
     bool ref_model = true, fit_grid = true;
     int bounces = 0;
     std::string linear;
+    std::vector<vct_light> lights;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--model=reference") ref_model = true;
@@ -37,12 +95,19 @@ int main(int argc, char** argv) {
         else if (a == "--bounces" && i + 1 < argc) bounces = std::atoi(argv[++i]);
         else if (a.rfind("--bounces=", 0) == 0) bounces = std::atoi(a.c_str() + 10);
         else if (a.rfind("--linear=", 0) == 0) linear = a.substr(9);
+        else if ((a == "--light" && i + 1 < argc) || a.rfind("--light=", 0) == 0) {
+            const std::string spec = a == "--light" ? argv[++i] : a.substr(8);
+            vct_light l;
+            if (!parse_light(spec, &l)) { std::fprintf(stderr, "malformed --light %s\n", spec.c_str()); return 2; }
+            lights.push_back(l);
+        }
         else if (a.rfind("--", 0) == 0) { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
         else pos.push_back(a);
     }
     if (pos.empty()) {
         std::fprintf(stderr, "usage: %s model.obj [grid] [width] [height] [frames] [out.ppm] [devices] "
-                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32]\n",
+                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] "
+                             "[--light dir:d:rgb | point:p:rgb:range | spot:p:d:rgb:range:inner:outer]...\n",
                      argv[0]);
         return 2;
     }
@@ -56,6 +121,7 @@ int main(int argc, char** argv) {
     if (s.grid < 4) { std::fprintf(stderr, "grid must be >= 4\n"); return 2; }
     if (bounces < 0) { std::fprintf(stderr, "--bounces must be >= 0\n"); return 2; }
     s.bounces = (uint32_t)bounces;
+    s.lights = lights;
     if (ref_model) ReferenceModelMatrix(s.model);
 
     AssetsManager& A = AssetsManager::Instance();            // assets.cpp:22-45

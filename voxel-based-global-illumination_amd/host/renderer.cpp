@@ -66,7 +66,12 @@ bool ConeTraceRenderer::rebuild_scene() {
                                      (uint32_t)(kd4.size() / 4), (uint32_t)offsetof(Vertex, TexCoords)),
                "vct_voxelize_textured"))
         return false;
-    if (!check(vct_inject_directional(ctx_, s_.light_dir, s_.light_color), "vct_inject_directional")) return false;
+    if (!s_.lights.empty()) {
+        if (!check(vct_inject_lights(ctx_, s_.lights.data(), (uint32_t)s_.lights.size()), "vct_inject_lights"))
+            return false;
+    } else if (!check(vct_inject_directional(ctx_, s_.light_dir, s_.light_color), "vct_inject_directional")) {
+        return false;
+    }
     if (!check(vct_build_mips(ctx_), "vct_build_mips")) return false;
     if (s_.bounces && !check(vct_inject_bounces(ctx_, s_.bounces), "vct_inject_bounces")) return false;
     scene_dirty_ = false;
@@ -101,6 +106,16 @@ void ConeTraceRenderer::Render() {
     check(vct_memcpy(ctx_, &last_steps_, counter_, 8, 1), "read counter");
 }
 
+vct_status ConeTraceRenderer::composite(float* lin, uint32_t* rgba) {
+    const float *pos = (const float*)gb_[0], *nrm = (const float*)gb_[1], *alb = (const float*)gb_[2];
+    const float *diff = (const float*)out_[0], *spec = (const float*)out_[1];
+    if (!s_.lights.empty())
+        return vct_composite_lights_device(ctx_, pos, nrm, alb, diff, spec, s_.width, s_.height, s_.lights.data(),
+                                           (uint32_t)s_.lights.size(), lin, rgba);
+    return vct_composite_device(ctx_, pos, nrm, alb, diff, spec, s_.width, s_.height, s_.light_dir, s_.light_color,
+                                lin, rgba);
+}
+
 bool ConeTraceRenderer::WritePPM(const std::string& path) {
     // row f3: composite + present on the device (include/vct.h vct_composite_device), then dump
     if (!ctx_) return false;
@@ -108,10 +123,7 @@ bool ConeTraceRenderer::WritePPM(const std::string& path) {
     void* rgba = nullptr;
     if (!check(vct_device_alloc(ctx_, px * 4, &rgba), "alloc rgba8")) return false;
     std::vector<uint32_t> img(px);
-    const bool ok = check(vct_composite_device(ctx_, (const float*)gb_[0], (const float*)gb_[1], (const float*)gb_[2],
-                                               (const float*)out_[0], (const float*)out_[1], s_.width, s_.height,
-                                               s_.light_dir, s_.light_color, nullptr, (uint32_t*)rgba),
-                          "vct_composite_device") &&
+    const bool ok = check(composite(nullptr, (uint32_t*)rgba), "composite") &&
                     check(vct_memcpy(ctx_, img.data(), rgba, px * 4, 1), "download rgba8");
     vct_device_free(ctx_, rgba);
     if (!ok) return false;
@@ -138,10 +150,7 @@ bool ConeTraceRenderer::WriteLinear(const std::string& path) {
     void* lin = nullptr;
     if (!check(vct_device_alloc(ctx_, px * 16, &lin), "alloc linear frame")) return false;
     std::vector<float> img(px * 4);
-    const bool ok = check(vct_composite_device(ctx_, (const float*)gb_[0], (const float*)gb_[1], (const float*)gb_[2],
-                                               (const float*)out_[0], (const float*)out_[1], s_.width, s_.height,
-                                               s_.light_dir, s_.light_color, (float*)lin, nullptr),
-                          "vct_composite_device") &&
+    const bool ok = check(composite((float*)lin, nullptr), "composite") &&
                     check(vct_memcpy(ctx_, img.data(), lin, px * 16, 1), "download linear frame");
     vct_device_free(ctx_, lin);
     if (!ok) return false;

@@ -36,6 +36,9 @@ struct ConeTraceSettings {
     uint32_t devices = 1;                 // > 1: one context over that many GPUs (vct_create_multi)
     uint32_t bounces = 0;                 // light bounces added to the grid after each inject + build
                                           // (vct_inject_bounces; 0: direct light only)
+    // a light list (include/vct_lights.h): when non-empty it replaces light_dir / light_color
+    // in K2 (vct_inject_lights) and in the composite (vct_composite_lights_device)
+    std::vector<vct_light> lights;
     // model matrix applied to the model's vertices before K1, column-major; main.cpp
     // sets the reference's T(0,-1.75,0) S(0.2) (r_voxelization.cpp:26-29) by default
     float model[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
@@ -60,6 +63,8 @@ public:
 private:
     bool check(vct_status s, const char* what);
     bool rebuild_scene();
+    // row f3 into `lin` (float4) or `rgba` (packed 8-bit), with the light list when there is one
+    vct_status composite(float* lin, uint32_t* rgba);
 
     std::string model_name_;
     ConeTraceSettings s_;

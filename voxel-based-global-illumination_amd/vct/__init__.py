@@ -28,10 +28,10 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import VCT_ALL_RANKS, VctCamera, VctCommId, VctConfig, VctTexture, VctTraceArgs
+from ._lib import VCT_ALL_RANKS, VctCamera, VctCommId, VctConfig, VctLight, VctTexture, VctTraceArgs
 
 __all__ = ["Context", "VctError", "VctConfig", "VctCamera", "tiles_for_rank", "tile_offset", "VERTEX_FLOATS",
-           "VCT_ALL_RANKS", "comm_frame_layout"]
+           "VCT_ALL_RANKS", "comm_frame_layout", "VctLight", "directional_light", "point_light", "spot_light"]
 
 VERTEX_FLOATS = 14          # reference Vertex: Position, Normal, TexCoords, Tangent, Bitangent
 VERTEX_STRIDE = VERTEX_FLOATS * 4
@@ -50,6 +50,46 @@ def _fptr(a: np.ndarray):
 
 def _f3(v):
     return (C.c_float * 3)(*[float(x) for x in v])
+
+
+def directional_light(dir_to_light, color=(1.0, 1.0, 1.0)) -> VctLight:
+    """A vct_light of type VCT_LIGHT_DIRECTIONAL: `dir_to_light` as inject_directional takes it."""
+    l = VctLight()
+    l.type = _lib.VCT_LIGHT_DIRECTIONAL
+    l.direction, l.color = _f3(dir_to_light), _f3(color)
+    return l
+
+
+def point_light(position, color=(1.0, 1.0, 1.0), range: float = 1.0) -> VctLight:
+    """A vct_light of type VCT_LIGHT_POINT at world `position`; no light at distance >= range."""
+    l = VctLight()
+    l.type = _lib.VCT_LIGHT_POINT
+    l.position, l.color, l.range = _f3(position), _f3(color), float(range)
+    return l
+
+
+def spot_light(position, direction, color=(1.0, 1.0, 1.0), range: float = 1.0, inner_deg: float = 20.0,
+               outer_deg: float = 30.0, cos_inner: float | None = None, cos_outer: float | None = None) -> VctLight:
+    """A vct_light of type VCT_LIGHT_SPOT shining along `direction`: full intensity inside
+    the half-angle inner_deg, none outside outer_deg.  The angles are degrees and become
+    cosines in float32 (np.cos of the float32 radians); cos_inner / cos_outer give the
+    cosines directly instead."""
+    l = VctLight()
+    l.type = _lib.VCT_LIGHT_SPOT
+    l.position, l.direction, l.color, l.range = _f3(position), _f3(direction), _f3(color), float(range)
+    l.cos_inner = float(np.cos(np.deg2rad(np.float32(inner_deg)))) if cos_inner is None else float(cos_inner)
+    l.cos_outer = float(np.cos(np.deg2rad(np.float32(outer_deg)))) if cos_outer is None else float(cos_outer)
+    return l
+
+
+def _light_array(lights):
+    lights = list(lights)
+    arr = (VctLight * max(len(lights), 1))()
+    for i, l in enumerate(lights):
+        if not isinstance(l, VctLight):
+            raise VctError(_EINVAL, f"lights[{i}]: expected a VctLight (vct.point_light, ...), got {type(l).__name__}")
+        arr[i] = l
+    return arr, len(lights)
 
 
 def tiles_for_rank(w: int, h: int, rank: int, world: int) -> int:
@@ -249,6 +289,13 @@ class Context:
         c = (C.c_float * 3)(*[float(x) for x in color])
         self._check(self.lib.vct_inject_directional(self.h, l, c), "inject")
 
+    def inject_lights(self, lights):
+        """vct_inject_lights: K2 for a list of VctLight (vct.directional_light / point_light /
+        spot_light), summed in list order; replaces level 0 as inject_directional does."""
+        fn = _lib.bind_light_extension(self.lib, "vct_inject_lights")
+        arr, n = _light_array(lights)
+        self._check(fn(self.h, arr, n), "inject_lights")
+
     def build_mips(self):
         self._check(self.lib.vct_build_mips(self.h), "build_mips")
 
@@ -400,6 +447,18 @@ class Context:
             self.h, *self._gbuf_ptrs(width, height, pos4, nrm4, alb4), self._dev(diffuse4, "diffuse4", _F32, n),
             self._dev(spec4, "spec4", _F32, n), width, height, l, c, self._dev(out_linear4, "out_linear4", _F32, n),
             self._dev(out_rgba8, "out_rgba8", _I32, width * height)), "composite")
+
+    def composite_lights_device(self, pos4, nrm4, alb4, diffuse4, spec4, width, height, lights,
+                                out_linear4=None, out_rgba8=None):
+        """composite_device with the direct term summed over a list of VctLight."""
+        fn = _lib.bind_light_extension(self.lib, "vct_composite_lights_device")
+        arr, nl = _light_array(lights)
+        n = 4 * width * height
+        self._check(fn(
+            self.h, *self._gbuf_ptrs(width, height, pos4, nrm4, alb4), self._dev(diffuse4, "diffuse4", _F32, n),
+            self._dev(spec4, "spec4", _F32, n), width, height, arr, nl,
+            self._dev(out_linear4, "out_linear4", _F32, n),
+            self._dev(out_rgba8, "out_rgba8", _I32, width * height)), "composite_lights")
 
     # -- grid access ------------------------------------------------------
     def download_level(self, level: int, face: int = 0) -> np.ndarray:

@@ -34,6 +34,11 @@ EXPORTS = (
 # symbols -- the CPU oracle backend -- still loads and binds.
 EXTENSIONS = ("vct_inject_bounces", "vct_bounce_sources")
 
+# include/vct_lights.h: point and spot lights, likewise HIP only (bind_light_extension)
+LIGHT_EXTENSIONS = ("vct_inject_lights", "vct_composite_lights_device")
+VCT_LIGHT_DIRECTIONAL, VCT_LIGHT_POINT, VCT_LIGHT_SPOT = 0, 1, 2
+VCT_MAX_LIGHTS = 64
+
 STATUS = {0: "VCT_OK", 1: "VCT_EINVAL", 2: "VCT_ENOMEM", 3: "VCT_EDEVICE", 4: "VCT_ECOMM", 5: "VCT_ESTATE"}
 
 
@@ -63,6 +68,19 @@ class VctCamera(C.Structure):
 
 class VctTexture(C.Structure):
     _fields_ = [("rgba8", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
+class VctLight(C.Structure):          # vct_light, 60 bytes
+    _fields_ = [
+        ("type", C.c_uint32),
+        ("position", C.c_float * 3),
+        ("direction", C.c_float * 3),
+        ("color", C.c_float * 3),
+        ("range", C.c_float),
+        ("cos_inner", C.c_float),
+        ("cos_outer", C.c_float),
+        ("reserved", C.c_uint32 * 2),
+    ]
 
 
 class VctCommId(C.Structure):
@@ -197,6 +215,48 @@ def bind_extension(lib: C.CDLL, name: str):
     fn.restype = res
     fn.argtypes = args
     return fn
+
+
+def bind_light_extension(lib: C.CDLL, name: str):
+    """The include/vct_lights.h function `name` of `lib`, with its signature declared;
+    AttributeError (naming the library) if this implementation does not export it."""
+    P, u32, i32 = C.c_void_p, C.c_uint32, C.c_int32
+    sig = {
+        "vct_inject_lights": (i32, [P, C.POINTER(VctLight), u32]),
+        "vct_composite_lights_device": (i32, [P, P, P, P, P, P, u32, u32, C.POINTER(VctLight), u32, P, P]),
+    }
+    res, args = sig[name]
+    try:
+        fn = getattr(lib, name)
+    except AttributeError:
+        raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
+                             "(include/vct_lights.h is implemented by the HIP library only)") from None
+    fn.restype = res
+    fn.argtypes = args
+    return fn
+
+
+def debug_lights(lib: C.CDLL, form: int = -1, pair_cap: int = 0, count: bool = False, route: bool = True):
+    """Tool / test hook (vct_debug_lights, not part of the headers), process-wide: the form
+    vct_inject_lights runs (-1 the shipped one, 0 one light per pass, 1 batched pairs), a cap
+    on the pair list in entries (0: the default), cell counting, and whether a list of one
+    directional light goes to vct_inject_directional's kernels."""
+    fn = lib.vct_debug_lights
+    fn.restype = None
+    fn.argtypes = [C.c_int, C.c_uint32, C.c_int, C.c_int]
+    fn(form, pair_cap, 1 if count else 0, 1 if route else 0)
+
+
+def debug_lights_stats(lib: C.CDLL, handle):
+    """(pairs walked, cells stepped) of the context's last vct_inject_lights (cells only
+    with counting on, debug_lights); waits for the ctx stream."""
+    fn = lib.vct_debug_lights_stats
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 2)()
+    if fn(handle, out) != 0:
+        return None
+    return int(out[0]), int(out[1])
 
 
 def debug_zmap(lib: C.CDLL, handle, m: int):
