@@ -403,5 +403,7 @@ vct_status vct_dump_info(const char* stem, vct_config* cfg, uint32_t* what);
 #include "vct_bounce.h"
 /* ---- point and spot lights (additive; HIP library only) -------------------------- */
 #include "vct_lights.h"
+/* ---- cone-traced soft shadows (additive; HIP library only) ------------------------ */
+#include "vct_shadow.h"
 
 #endif /* VCT_H */

@@ -211,4 +211,46 @@
  *  vct_composite_device bit for bit (x * 1.0f and +0 + x are exact for x >= 0), and the
  *  order of the list is part of the result. */
 
+/* ---- shadow cones (vct_shadow_cones_device / vct_composite_shadowed_device,
+ *      include/vct_shadow.h; no new literals) ---------------------------------------------
+ *  Receiver: a pixel with pos.w != 0.  Its q and N, and per light l, f, ndl, t_lim and the
+ *  skip rule, are those of "local lights" (the composite receiver), in list order.
+ *  tan_half[j] == 0:  V is the "local lights" shadow walk, unchanged (V in {0, 1}).
+ *  Otherwise:  tau = fminf(fmaxf(tan_half[j], VCT_SPEC_TAU_MIN), VCT_SPEC_TAU_MAX), and the
+ *  march is the alpha component of A.6 with o = q, d = l, a = 0, t = 1, L = log2 n,
+ *  t_max = (float)n * VCT_SQRT3:
+ *    1. Before each sample, in this order:
+ *         end if !(a < VCT_ALPHA_STOP)                     (alpha stop)
+ *         end if !(t <= t_max)
+ *         end if t >= t_lim                                (the light is reached)
+ *         p_c = o_c + d_c * t  (multiply, then add; no fma);  end if p is outside [0, n]^3,
+ *         that is unless 0 <= p_c <= n for every c         (left the grid)
+ *    2. D = fmaxf(1.0f, (2.0f * tau) * t);  m = fminf(log2(D), (float)L) with the log2 of
+ *       VCT_LOG2_*;  l0 = (int)m;  fr = m - (float)l0
+ *    3. s = the alpha of D_l0(p, d) exactly as A.5 computes it: texel coordinates
+ *       c = p * 2^-l0 - 0.5f (the product is exact), i = floorf(c), w = c - i, the two
+ *       weights per axis (1.0f - w, w); faces chosen by d_c >= 0;
+ *       face weights d_c * d_c; per corner texel v = fmaf(dz2, Fz, fmaf(dy2, Fy, dx2 * Fx));
+ *       trilinear acc = fmaf(wc, v, acc) over the eight corners, x fastest, from acc = +0,
+ *       with wc = (wx * wy) * wz; texels outside the level are zero (zero border); level 0,
+ *       and every level of an aniso = 0 grid, use the one volume (v = its texel).
+ *    4. If fr > 0 and l0 < L:  s1 = the same of level l0 + 1;
+ *       s = fmaf(fr, s1, (1.0f - fr) * s)
+ *    5. a = fmaf(1.0f - a, s, a);  t = t + VCT_STEP_SCALE * D;  one cone step counted.
+ *  The rgb channels never enter a, so this is A.6's march reduced to one channel plus the
+ *  t >= t_lim end: a cone that is never limited (a directional light) takes exactly the
+ *  steps of the A.6 cone with the same o, d and tau, and ends with its alpha, bit for bit.
+ *  Visibility:  V = fmaxf(1.0f - a / VCT_ALPHA_STOP, 0.0f), one correctly rounded divide.
+ *  A cone that saturates (a >= VCT_ALPHA_STOP) is fully dark; a cone that meets nothing
+ *  (a = +0) gives exactly 1.
+ *  The start (o = q = P' + N, t = 1) is K4's, and so is its known weakness: on a coarse
+ *  grid a cone that leaves its surface at a grazing angle samples the surface's own voxels
+ *  in its first steps and darkens itself.  No other offset is introduced here.
+ *  The vis plane: vis[j][y][x] = V for a pair that is not skipped; +0 for a skipped pair
+ *  and for a background pixel (pos.w == 0).
+ *  Composite: contrib_c = (((A_c * color_c) * ndl) * f) * vis[j][px], summed over the
+ *  lights not skipped in list order and finished as "local lights"
+ *  (final = (direct + A * D) + S).  With every tan_half 0 it is vct_composite_lights_device
+ *  bit for bit. */
+
 #endif /* VCT_SPEC_H */

@@ -341,6 +341,7 @@ void vct_destroy(vct_ctx* c) {
             if (s.p) (void)hipFree(s.p);
     if (c->ev) (void)hipEventDestroy(c->ev);
     if (c->xchg_done) (void)hipEventDestroy(c->xchg_done);
+    if (c->shadow_done) (void)hipEventDestroy(c->shadow_done);
     for (auto& en : c->k4tune.e) {
         for (auto& f : en.ev)
             for (auto& sl : f)

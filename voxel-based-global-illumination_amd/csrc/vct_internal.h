@@ -230,7 +230,18 @@ struct vct_ctx {
     vct::Textures tex;
     vct::Scratch scratch[12];    // reusable scratch (0 trace host staging, 1 voxelize temps,
                                   // 2-3 G-buffer bins, 4 K2 work list, 7 K1 candidate bucket table,
-                                  // 8 multi-device tiles / gather, 9 multi-device step counters)
+                                  // 8 multi-device tiles / gather, 9 multi-device step counters,
+                                  // 10 shadow-cone step tables)
+    float shadow_tau[VCT_MAX_LIGHTS] = {};   // the apertures whose step tables scratch 10 holds, slot by slot
+    uint32_t shadow_taus = 0;                // (vct_shadow.hip; 0: none built yet)
+    // The tables are shared by every vct_shadow_cones_device call whatever stream the caller
+    // sets: a call on another stream than the previous one first makes its stream wait for that
+    // call's end (`shadow_done`, recorded after every march), so a table is never read before
+    // the launch that builds it has run, nor rewritten while an earlier march reads it; the
+    // event of the last call also covers every earlier one (as xchg_done below).
+    hipEvent_t shadow_done = nullptr;
+    hipStream_t shadow_stream = nullptr;
+    int shadow_path = 0;                     // address path of the last march: 32 or 64 (vct_debug_shadow_path)
     vct::StreamScratch k4s[vct::kStreamSets];   // K4 hand-over + reorder scratch per stream (k4_scratch)
     vct::K4Tuner k4tune;                // timed-form choice of the default cone trace
     vct::Bounce bounce;                 // source list of vct_inject_bounces

@@ -5,7 +5,7 @@
 //
 //   vct_headless <model.obj> [grid=256] [width=800] [height=600] [frames=5] [out.ppm] [devices=1]
 //                [--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32]
-//                [--light SPEC]...
+//                [--light SPEC]... [--shadow-tan T]
 //   (devices > 1: one process drives that many GPUs through vct_create_multi)
 //   --model: the model matrix of the reference's draw, T(0,-1.75,0) S(0.2)
 //            (r_voxelization.cpp:26-29; default), or none;
@@ -14,6 +14,9 @@
 //   --bounces: light bounces added to the grid after each inject + build
 //            (vct_inject_bounces; default 0);
 //   --linear: also dump the last frame before tone mapping (raw float32 [h][w][4]).
+//   --shadow-tan: T > 0 shades the direct term with shadow cones of half-angle tangent T toward
+//            every light of the frame (include/vct_shadow.h) instead of the hard voxel walk;
+//            0 (the default) keeps the walk;
 //   --light:  one light of a light list (include/vct_lights.h), repeatable, in list order; with
 //            any --light the list replaces the default directional light.  SPEC is colon-
 //            separated fields of comma-separated floats, world units, angles in degrees:
@@ -86,6 +89,7 @@ int main(int argc, char** argv) {
     int bounces = 0;
     std::string linear;
     std::vector<vct_light> lights;
+    float shadow_tan = 0.0f;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--model=reference") ref_model = true;
@@ -95,6 +99,8 @@ int main(int argc, char** argv) {
         else if (a == "--bounces" && i + 1 < argc) bounces = std::atoi(argv[++i]);
         else if (a.rfind("--bounces=", 0) == 0) bounces = std::atoi(a.c_str() + 10);
         else if (a.rfind("--linear=", 0) == 0) linear = a.substr(9);
+        else if (a == "--shadow-tan" && i + 1 < argc) shadow_tan = std::strtof(argv[++i], nullptr);
+        else if (a.rfind("--shadow-tan=", 0) == 0) shadow_tan = std::strtof(a.c_str() + 13, nullptr);
         else if ((a == "--light" && i + 1 < argc) || a.rfind("--light=", 0) == 0) {
             const std::string spec = a == "--light" ? argv[++i] : a.substr(8);
             vct_light l;
@@ -106,7 +112,7 @@ int main(int argc, char** argv) {
     }
     if (pos.empty()) {
         std::fprintf(stderr, "usage: %s model.obj [grid] [width] [height] [frames] [out.ppm] [devices] "
-                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] "
+                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] "
                              "[--light dir:d:rgb | point:p:rgb:range | spot:p:d:rgb:range:inner:outer]...\n",
                      argv[0]);
         return 2;
@@ -120,7 +126,9 @@ int main(int argc, char** argv) {
     if (pos.size() > 6) s.devices = (uint32_t)std::atoi(pos[6].c_str());
     if (s.grid < 4) { std::fprintf(stderr, "grid must be >= 4\n"); return 2; }
     if (bounces < 0) { std::fprintf(stderr, "--bounces must be >= 0\n"); return 2; }
+    if (!(shadow_tan >= 0.0f) || !std::isfinite(shadow_tan)) { std::fprintf(stderr, "--shadow-tan must be finite and >= 0\n"); return 2; }
     s.bounces = (uint32_t)bounces;
+    s.shadow_tan = shadow_tan;
     s.lights = lights;
     if (ref_model) ReferenceModelMatrix(s.model);
 

@@ -36,6 +36,7 @@ ConeTraceRenderer::~ConeTraceRenderer() {
     for (void* p : gb_) vct_device_free(ctx_, p);
     for (void* p : out_) vct_device_free(ctx_, p);
     vct_device_free(ctx_, counter_);
+    if (vis_) vct_device_free(ctx_, vis_);
     vct_destroy(ctx_);
 }
 
@@ -109,6 +110,30 @@ void ConeTraceRenderer::Render() {
 vct_status ConeTraceRenderer::composite(float* lin, uint32_t* rgba) {
     const float *pos = (const float*)gb_[0], *nrm = (const float*)gb_[1], *alb = (const float*)gb_[2];
     const float *diff = (const float*)out_[0], *spec = (const float*)out_[1];
+    if (s_.shadow_tan > 0.0f) {   // soft shadows: V per (light, pixel) from shadow cones, then the composite over it
+        std::vector<vct_light> lights = s_.lights;
+        if (lights.empty()) {     // the default directional light as a list of one
+            vct_light l{};
+            l.type = VCT_LIGHT_DIRECTIONAL;
+            for (int k = 0; k < 3; ++k) { l.direction[k] = s_.light_dir[k]; l.color[k] = s_.light_color[k]; }
+            lights.push_back(l);
+        }
+        const std::vector<float> tan_half(lights.size(), s_.shadow_tan);
+        const size_t need = lights.size() * (size_t)s_.width * s_.height * sizeof(float);
+        if (need > vis_bytes_) {   // the planes stay with the renderer, as gb_ and out_ do
+            if (vis_) vct_device_free(ctx_, vis_);
+            vis_ = nullptr;
+            vis_bytes_ = 0;
+            const vct_status st = vct_device_alloc(ctx_, need, &vis_);
+            if (st != VCT_OK) return st;
+            vis_bytes_ = need;
+        }
+        const vct_status st = vct_shadow_cones_device(ctx_, pos, nrm, s_.width, s_.height, lights.data(),
+                                                      (uint32_t)lights.size(), tan_half.data(), (float*)vis_, nullptr);
+        if (st != VCT_OK) return st;
+        return vct_composite_shadowed_device(ctx_, pos, nrm, alb, diff, spec, s_.width, s_.height, lights.data(),
+                                             (uint32_t)lights.size(), (const float*)vis_, lin, rgba);
+    }
     if (!s_.lights.empty())
         return vct_composite_lights_device(ctx_, pos, nrm, alb, diff, spec, s_.width, s_.height, s_.lights.data(),
                                            (uint32_t)s_.lights.size(), lin, rgba);

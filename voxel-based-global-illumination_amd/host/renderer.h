@@ -39,6 +39,9 @@ struct ConeTraceSettings {
     // a light list (include/vct_lights.h): when non-empty it replaces light_dir / light_color
     // in K2 (vct_inject_lights) and in the composite (vct_composite_lights_device)
     std::vector<vct_light> lights;
+    // > 0: the composite's direct term is shadowed by cones of this half-angle tangent toward
+    // every light of the frame (include/vct_shadow.h) instead of the hard voxel walk; 0: the walk
+    float shadow_tan = 0.0f;
     // model matrix applied to the model's vertices before K1, column-major; main.cpp
     // sets the reference's T(0,-1.75,0) S(0.2) (r_voxelization.cpp:26-29) by default
     float model[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
@@ -72,6 +75,8 @@ private:
     void* gb_[3] = {nullptr, nullptr, nullptr};
     void* out_[2] = {nullptr, nullptr};
     void* counter_ = nullptr;
+    void* vis_ = nullptr;                 // V planes of the soft-shadow composite (shadow_tan > 0), kept
+    size_t vis_bytes_ = 0;
     bool scene_dirty_ = true;
     vct_status status_ = VCT_OK;
     std::string error_;

@@ -460,6 +460,35 @@ class Context:
             self._dev(out_linear4, "out_linear4", _F32, n),
             self._dev(out_rgba8, "out_rgba8", _I32, width * height)), "composite_lights")
 
+    def shadow_cones_device(self, pos4, nrm4, width, height, lights, tan_half, vis, cone_steps=None):
+        """vct_shadow_cones_device: V in [0, 1] for every (light, pixel) into vis, a float32
+        device tensor [len(lights), height, width].  tan_half: one half-angle tangent per
+        light; 0 keeps the hard voxel walk for that light.  cone_steps: a 1-element int64
+        device tensor that the call adds its cone steps to."""
+        fn = _lib.bind_shadow_extension(self.lib, "vct_shadow_cones_device")
+        arr, nl = _light_array(lights)
+        tan_half = [float(t) for t in tan_half]
+        if len(tan_half) != nl:
+            raise VctError(_EINVAL, f"shadow_cones: {len(tan_half)} tan_half values for {nl} lights")
+        th = (C.c_float * max(nl, 1))(*tan_half)
+        n = 4 * width * height
+        self._check(fn(self.h, self._dev(pos4, "pos4", _F32, n), self._dev(nrm4, "nrm4", _F32, n), width, height,
+                       arr, nl, th, self._dev(vis, "vis", _F32, nl * width * height),
+                       self._dev(cone_steps, "cone_steps", _I64, 1)), "shadow_cones")
+
+    def composite_shadowed_device(self, pos4, nrm4, alb4, diffuse4, spec4, width, height, lights, vis,
+                                  out_linear4=None, out_rgba8=None):
+        """composite_lights_device with V read from vis (shadow_cones_device's output)."""
+        fn = _lib.bind_shadow_extension(self.lib, "vct_composite_shadowed_device")
+        arr, nl = _light_array(lights)
+        n = 4 * width * height
+        self._check(fn(
+            self.h, *self._gbuf_ptrs(width, height, pos4, nrm4, alb4), self._dev(diffuse4, "diffuse4", _F32, n),
+            self._dev(spec4, "spec4", _F32, n), width, height, arr, nl,
+            self._dev(vis, "vis", _F32, nl * width * height),
+            self._dev(out_linear4, "out_linear4", _F32, n),
+            self._dev(out_rgba8, "out_rgba8", _I32, width * height)), "composite_shadowed")
+
     # -- grid access ------------------------------------------------------
     def download_level(self, level: int, face: int = 0) -> np.ndarray:
         nl, _ = self.level_dims(level)

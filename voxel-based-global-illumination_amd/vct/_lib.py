@@ -39,6 +39,9 @@ LIGHT_EXTENSIONS = ("vct_inject_lights", "vct_composite_lights_device")
 VCT_LIGHT_DIRECTIONAL, VCT_LIGHT_POINT, VCT_LIGHT_SPOT = 0, 1, 2
 VCT_MAX_LIGHTS = 64
 
+# include/vct_shadow.h: cone-traced soft shadows, likewise HIP only (bind_shadow_extension)
+SHADOW_EXTENSIONS = ("vct_shadow_cones_device", "vct_composite_shadowed_device")
+
 STATUS = {0: "VCT_OK", 1: "VCT_EINVAL", 2: "VCT_ENOMEM", 3: "VCT_EDEVICE", 4: "VCT_ECOMM", 5: "VCT_ESTATE"}
 
 
@@ -234,6 +237,43 @@ def bind_light_extension(lib: C.CDLL, name: str):
     fn.restype = res
     fn.argtypes = args
     return fn
+
+
+def bind_shadow_extension(lib: C.CDLL, name: str):
+    """The include/vct_shadow.h function `name` of `lib`, with its signature declared;
+    AttributeError (naming the library) if this implementation does not export it."""
+    P, u32, i32 = C.c_void_p, C.c_uint32, C.c_int32
+    sig = {
+        "vct_shadow_cones_device": (i32, [P, P, P, u32, u32, C.POINTER(VctLight), u32, C.POINTER(C.c_float), P, P]),
+        "vct_composite_shadowed_device": (i32, [P, P, P, P, P, P, u32, u32, C.POINTER(VctLight), u32, P, P, P]),
+    }
+    res, args = sig[name]
+    try:
+        fn = getattr(lib, name)
+    except AttributeError:
+        raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
+                             "(include/vct_shadow.h is implemented by the HIP library only)") from None
+    fn.restype = res
+    fn.argtypes = args
+    return fn
+
+
+def debug_shadow(lib: C.CDLL, force64: bool = False):
+    """Test hook (vct_debug_shadow, not part of the headers), process-wide: send every grid
+    through the 64-bit-address path of the shadow cones (the one 1024^3 takes)."""
+    fn = lib.vct_debug_shadow
+    fn.restype = None
+    fn.argtypes = [C.c_int]
+    fn(1 if force64 else 0)
+
+
+def debug_shadow_path(lib: C.CDLL, handle) -> int:
+    """Test hook (vct_debug_shadow_path): the address path the context's last shadow-cone
+    march was launched with -- 32 (buffer resources), 64 (64-bit addresses), 0 before any."""
+    fn = lib.vct_debug_shadow_path
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p]
+    return int(fn(handle))
 
 
 def debug_lights(lib: C.CDLL, form: int = -1, pair_cap: int = 0, count: bool = False, route: bool = True):
