@@ -83,7 +83,11 @@ typedef struct vct_camera {
 } vct_camera;
 
 /* Arguments of the device-resident cone trace (K4).  Float buffers must be
- * 16-byte aligned, the two counters 8-byte aligned (VCT_EINVAL otherwise). */
+ * 16-byte aligned, the two counters 8-byte aligned (VCT_EINVAL otherwise).
+ * Any pos4.w != 0 (NaN and denormals included; -0 is background) is a valid pixel; pixels
+ * outside the grid, with a non-finite position or normal component, or with a zero or scaled
+ * normal (tested from 1e-20 to 4 times unit length) are legal and give the spec's result
+ * (tests/trace_inputs.py lists what is tested). */
 typedef struct vct_trace_args {
     const float* pos4;     /* device [h][w][4]: world position, w = 1 valid / 0 background */
     const float* nrm4;     /* device [h][w][4]: unit normal                                */

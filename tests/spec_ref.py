@@ -25,8 +25,38 @@ _pack, _unpack = struct.Struct("<f").pack, struct.Struct("<f").unpack
 
 
 def f32(x: float) -> float:
-    """Round a Python float to the nearest binary32 (ties to even)."""
-    return _unpack(_pack(x))[0]
+    """Round a Python float to the nearest binary32 (ties to even; overflow gives +-inf)."""
+    try:
+        return _unpack(_pack(x))[0]
+    except OverflowError:           # struct raises exactly where the rounding overflows
+        return math.copysign(math.inf, x)
+
+
+def fdiv(a: float, b: float) -> float:
+    """IEEE a / b in binary64 (Python raises on a zero divisor): x/0 = +-inf, 0/0 = NaN."""
+    if b != 0.0:
+        return a / b
+    if a == 0.0 or a != a:
+        return math.nan
+    return math.copysign(math.inf, a) * math.copysign(1.0, b)
+
+
+def fminf(a: float, b: float) -> float:
+    """C fminf: a NaN operand is skipped (Python's min keeps or drops it by position)."""
+    if a != a:
+        return b
+    if b != b:
+        return a
+    return a if a < b else b
+
+
+def fmaxf(a: float, b: float) -> float:
+    """C fmaxf: a NaN operand is skipped."""
+    if a != a:
+        return b
+    if b != b:
+        return a
+    return a if a > b else b
 
 
 def _next32(x: float, up: bool) -> float:
@@ -37,6 +67,8 @@ def fmaf(a: float, b: float, c: float) -> float:
     """Correctly rounded binary32 fused multiply-add of binary32 values."""
     p = a * b                       # exact in binary64
     s = p + c
+    if not math.isfinite(s):        # inf / NaN operands (or inf - inf): IEEE gives p + c as it is
+        return s
     bb = s - p
     err = (p - (s - bb)) + (c - bb)  # TwoSum: p + c == s + err exactly
     r = f32(s)
@@ -387,9 +419,11 @@ class Tracer:
             q = [f32(o[i] + f32(d[i] * t)) for i in range(3)]
             if not all(0.0 <= v <= nf for v in q):
                 break
-            D = max(1.0, f32(tau2 * t))
-            m = min(log2(D), float(self.L))
-            l0 = int(m)
+            D = fmaxf(1.0, f32(tau2 * t))
+            m = log2(D)
+            if m > float(self.L):
+                m = float(self.L)
+            l0 = int(m)                 # D is finite and >= 1 (tau is clamped, t <= tmax): 0 <= m <= L
             fr = f32(m - l0)
             s = self._level(l0, q, faces, wd)
             if fr > 0 and l0 < self.L:
@@ -409,7 +443,7 @@ class Tracer:
         nx, ny, nz = (float(v) for v in N[:3])
         o = [f32(f32(f32(float(P[i]) - self.g0[i]) * self.inv_h) + float(N[i])) for i in range(3)]
         sgn = math.copysign(1.0, nz)
-        ka = f32(-1.0 / f32(sgn + nz))
+        ka = f32(fdiv(-1.0, f32(sgn + nz)))
         kb = f32(f32(nx * ny) * ka)
         T = [f32(1.0 + f32(f32(f32(sgn * nx) * nx) * ka)), f32(sgn * kb), -f32(sgn * nx)]
         B = [kb, f32(sgn + f32(f32(ny * ny) * ka)), -ny]
@@ -424,13 +458,13 @@ class Tracer:
         diff = irr + [f32(1.0 - occ)]
         spec = [0.0] * 4
         if specular:
-            v = [f32(float(eye[i]) - float(P[i])) for i in range(3)]
+            v = [f32(f32(float(eye[i])) - float(P[i])) for i in range(3)]   # the ABI's eye is binary32
             vl = f32(math.sqrt(f32(f32(f32(v[0] * v[0]) + f32(v[1] * v[1])) + f32(v[2] * v[2]))))
-            v = [f32(x / vl) for x in v]
+            v = [f32(fdiv(x, vl)) for x in v]
             ndv = f32(f32(f32(nx * v[0]) + f32(ny * v[1])) + f32(nz * v[2]))
             k2 = f32(2.0 * ndv)
             r = [f32(f32(k2 * n_) - v_) for n_, v_ in zip((nx, ny, nz), v)]
-            tau = min(max(float(rough), TAU_MIN), TAU_MAX)
+            tau = fminf(fmaxf(float(rough), TAU_MIN), TAU_MAX)
             spec, st = self.march(o, r, tau)
             steps += st
         return diff, spec, steps

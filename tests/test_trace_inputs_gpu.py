@@ -1,0 +1,506 @@
+"""K4 on hostile G-buffer pixels and on the specular step-table cache, bit for bit against
+the CPU oracle (tests/trace_inputs.py builds the inputs; tests/test_trace_inputs.py checks
+the reference itself).  Float outputs are compared through a uint32 view, steps_px and
+cone_steps must be equal: no tolerance anywhere.
+
+Every comparison takes the GPU's own level 0 and pyramid (as test_trace_parity does), grids
+are n = 16 and n = 32 and frames 64 x 48.  One catalogue family per test, so a difference
+names its family; the message names the first differing pixels and their entries.
+
+The other consumers of the frame (test_consumer_*) run every entry for which their reference
+defines a result.  Left out there, and why: pos_big+ and pos_big- (1e30) and the whole
+non-finite family.  The references' shadow walks start with a float -> int conversion of the
+cone origin ((int)floorf(q) in vo_composite, floor(q).astype(int64) in lights_ref.walk),
+which is undefined for a value no integer holds and for NaN.  Every other entry (the 1e3 E
+positions are about 1.6e4 voxels out and fit an int) is compared.
+
+On these grids g0 != 0, so pos_denorm's x offset is absorbed by g0 (its y is a
+true denormal); the CPU comparison in test_trace_inputs.py uses g0 = 0."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import trace_inputs as TI
+from helpers import gpu_pipeline, gpu_pyramid_flat
+
+pytestmark = pytest.mark.gpu
+F = np.float32
+W, H = 64, 48
+CONTEXTS = [("cornell", 16, True, 9), ("atrium", 32, False, 16)]
+UNION, OCC, SCREEN, REORDER, NO_TABLES = 0x1000000, 0x2000000, 0x4000000, 0x8000, 0x100
+# counted launches (steps_px and cone_steps): the forced forms in both ray orders, the tables
+# off, and the counted variant list of test_trace_variants_bitexact
+COUNTED = (UNION | SCREEN, UNION | REORDER, OCC | SCREEN, OCC | REORDER, NO_TABLES,
+           0, 1, 0x8000, 0x8001, 0x1000000, 0x2000000, 0x2008000, 0x4000000, 0x5000000)
+# its cone-split list (no steps_px: the cones split over workgroups, a specular order of its own)
+SPLIT = (0, 1, 0x100, 0x200, 0x400, 0x800, 0x400, 0x300400, 0x400400, 0x500400, 0x900400, 0x900400, 0x500400, 0,
+         0x8000, 0x8400, 0x8800, 0x8200, 0x8000, 0x1000000, 0x2000000, 0x2000400, 0x2000800, 0x2008000, 0x4000000,
+         0x6000000, 0x2400, 0x902400, 0x502400, 0x2002400, 0)
+# ... and its counter-free list (the form compiled without the counting instructions)
+PLAIN = (0, 0x4000, 0x400, 0x800, 0x200, 0x500400, 0x300400, 0x902400, 0)
+
+
+class Rig:
+    """One context with its scene, clean frame and oracle."""
+
+    def __init__(self, O, name, n, aniso, nd, specular=True, devices=0):
+        import torch
+        from vct import Context, scenes
+        from vct.camera import Camera
+        self.O, self.n, self.aniso, self.nd, self.specular = O, n, aniso, nd, specular
+        self.ctx, self.scene, self.arrays, (self.g0, self.E) = gpu_pipeline(n, name, aniso=aniso, n_diffuse=nd,
+                                                                            specular=specular)
+        self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+        cam = Camera()
+        self.eye = cam.position
+        self.clean = scenes.raycast_numpy(self.scene, cam, W, H)
+        self.dev = torch.device("cuda")
+        self.refresh()
+
+    def refresh(self):
+        self.r0, self.pyr = self.ctx.download_level(0), gpu_pyramid_flat(self.ctx)
+
+    def oracle(self, gb, eye=None):
+        return self.O.trace(self.n, self.g0, self.E, self.r0, self.pyr, *gb, self.eye if eye is None else eye,
+                            aniso=self.aniso, n_diffuse=self.nd, specular=self.specular)
+
+    def host(self, gb, eye=None, ctx=None):
+        return (ctx or self.ctx).trace(*gb, self.eye if eye is None else eye)
+
+    def device(self, gb, variant, eye=None, steps=True, count=True):
+        import torch
+        t = [torch.from_numpy(np.ascontiguousarray(a, F)).to(self.dev) for a in gb]
+        d = torch.full((H, W, 4), -1.0, device=self.dev)
+        sp = torch.full((H, W, 4), -1.0, device=self.dev)
+        st = torch.zeros((H, W), dtype=torch.int32, device=self.dev) if steps else None
+        cnt = torch.zeros(1, dtype=torch.int64, device=self.dev) if count else None
+        self.ctx.trace_device(*t, W, H, self.eye if eye is None else eye, d, sp, steps_px=st, cone_steps=cnt,
+                              variant=variant)
+        torch.cuda.synchronize()
+        return {"diffuse": d.cpu().numpy(), "spec": sp.cpu().numpy(),
+                "steps_px": st.cpu().numpy().astype(np.uint32) if steps else None,
+                "cone_steps": int(cnt[0]) if count else None}
+
+    def tiled(self, gb, world=3):
+        """compact ranks of a `world`-way tile partition, gathered with untile_planes_device"""
+        import torch
+        from vct.multi import tiles_for_rank
+        t = [torch.from_numpy(np.ascontiguousarray(a, F)).to(self.dev) for a in gb]
+        maxt = tiles_for_rank(W, H, 0, world)
+        g = torch.zeros((world, 2, maxt * 4096, 4), device=self.dev)
+        cnt = torch.zeros(1, dtype=torch.int64, device=self.dev)
+        for r in range(world):
+            self.ctx.trace_device(*t, W, H, self.eye, g[r, 0], g[r, 1], cone_steps=cnt, tile_rank=r, tile_world=world,
+                                  tile_compact=True)
+        d, sp = torch.zeros((H, W, 4), device=self.dev), torch.zeros((H, W, 4), device=self.dev)
+        self.ctx.untile_planes_device(g, W, H, world, (d, sp))
+        torch.cuda.synchronize()
+        return {"diffuse": d.cpu().numpy(), "spec": sp.cpu().numpy(), "steps_px": None, "cone_steps": int(cnt[0])}
+
+    def multi(self, gb, devices=2):
+        from vct import Context, scenes
+        c = Context(self.n, self.g0, self.E, aniso=self.aniso, n_diffuse=self.nd, specular=self.specular,
+                    devices=devices)
+        c.voxelize(*self.arrays)
+        c.inject_directional(scenes.LIGHT_DIR, scenes.LIGHT_COLOR)
+        c.build_mips()
+        try:
+            return self.host(gb, ctx=c)
+        finally:
+            c.close()
+
+    def close(self):
+        self.ctx.close()
+
+
+def same(got, ref, what, frame=None):
+    bad = TI.bits_equal(got, ref)
+    assert not bad, f"{what}: {bad} differ; {TI.describe_diff(got, ref, frame)}"
+
+
+def run_family(O, families, every_launch=True):
+    for name, n, aniso, nd in CONTEXTS:
+        rig = Rig(O, name, n, aniso, nd)
+        tag = f"{name}{n}/{'+'.join(families)}"
+        fr = TI.build(rig.clean, rig.g0, rig.E, n, families)
+        gb = (fr.pos, fr.nrm, fr.alb)
+        ref_clean = rig.oracle(rig.clean)
+        ref = rig.oracle(gb)
+        TI.check_reference(ref, ref_clean, fr, rig.clean)        # on the CPU, before any GPU comparison
+        same(rig.host(gb), ref, f"{tag} default", fr)
+        for v in COUNTED:
+            same(rig.device(gb, v), ref, f"{tag} variant {v:#x}", fr)
+        if every_launch:
+            for v in SPLIT:
+                same(rig.device(gb, v, steps=False), ref, f"{tag} variant {v:#x} (no steps_px)", fr)
+            for v in PLAIN:
+                same(rig.device(gb, v, steps=False, count=False), ref, f"{tag} variant {v:#x} (no counters)", fr)
+        same(rig.tiled(gb), ref, f"{tag} tile_world 3 compact", fr)
+        same(rig.multi(gb), ref, f"{tag} vct_create_multi, 2 devices", fr)
+        # nothing a hostile wave left behind (tuner state, brick cache, step tables) leaks forward
+        same(rig.host(rig.clean), ref_clean, f"{tag} the clean frame after the hostile one")
+        same(rig.device(rig.clean, REORDER, steps=False), ref_clean, f"{tag} the clean frame, reordered")
+        rig.close()
+
+
+def test_hostile_position(gpu_ready, oracle_mod):
+    """Finite positions outside the grid (0.5 h, 3 h, 1e3 E per axis and sign, +-1e30), cone
+    origins exactly 0 and exactly n, a denormal component: every launch form equals the oracle."""
+    run_family(oracle_mod, ("position",))
+
+
+def test_hostile_posw(gpu_ready, oracle_mod):
+    """pos.w = -0.0 (background), 2, -1, NaN and 1e-45 (valid; a compare that flushed the
+    denormal would differ)."""
+    run_family(oracle_mod, ("posw",))
+
+
+def test_hostile_normal(gpu_ready, oracle_mod):
+    """Zero, signed-zero, exact-axis and non-unit normals (x 0.5, x 4, x 1e-20)."""
+    run_family(oracle_mod, ("normal",))
+
+
+def test_hostile_roughness(gpu_ready, oracle_mod):
+    """alb.w = NaN, +-inf, -1, 0, TAU_MIN and its neighbours, 1 and its upper neighbour, 5."""
+    run_family(oracle_mod, ("roughness",))
+
+
+def test_hostile_nonfinite(gpu_ready, oracle_mod):
+    """One position or normal component NaN or +-inf: the oracle's inside test rejects the
+    cone's first position, so such a cone takes no step (and leaves its wave untouched)."""
+    run_family(oracle_mod, ("nonfinite",))
+
+
+def test_hostile_eye(gpu_ready, oracle_mod):
+    """The eye bit-equal to a pixel's position (vl = 0: a NaN reflection) and at 1e20 (v.v
+    overflows: a zero reflection, a cone that stays at its origin), over the clean frame and
+    the combined hostile frame, default variant and reordered."""
+    for name, n, aniso, nd in CONTEXTS:
+        rig = Rig(oracle_mod, name, n, aniso, nd)
+        fr = TI.build(rig.clean, rig.g0, rig.E, n)
+        on_px, _ = TI.eye_on_pixel(rig.clean)
+        for eye in (on_px, TI.EYE_FAR):
+            for what, gb, f in (("clean", rig.clean, None), ("combined", (fr.pos, fr.nrm, fr.alb), fr)):
+                ref = rig.oracle(gb, eye)
+                assert np.isfinite(ref["diffuse"]).all() and np.isfinite(ref["spec"]).all()
+                tag = f"{name}{n} eye {eye} {what}"
+                same(rig.host(gb, eye), ref, f"{tag} default", f)
+                same(rig.device(gb, REORDER, eye), ref, f"{tag} reordered", f)
+                same(rig.device(gb, REORDER, eye, steps=False), ref, f"{tag} reordered, split", f)
+                same(rig.device(gb, 1, eye), ref, f"{tag} per-lane gathers", f)
+        same(rig.host(rig.clean), rig.oracle(rig.clean), f"{name}{n} the clean frame afterwards")
+        rig.close()
+
+
+def test_hostile_combined(gpu_ready, oracle_mod):
+    """Every family in one frame (a block hostile in all 64 pixels, a block mixing all
+    families, 38 entries in blocks of their own, 8 blocks untouched)."""
+    run_family(oracle_mod, TI.FAMILIES)
+
+
+# ---------------------------------------------------------------------------
+# D  the specular step-table cache (kSpecSlots = 8 slots of 64 rows per context)
+# ---------------------------------------------------------------------------
+def _rough(rig, values, shift=0):
+    return (rig.clean[0], rig.clean[1], TI.block_roughness(rig.clean[2], values, shift))
+
+
+@pytest.mark.parametrize("nd", [9, 0])
+def test_tables_more_apertures_than_slots(gpu_ready, oracle_mod, nd):
+    """D.1, D.2, D.5, D.6 in one context (cornell 32; nd = 0: every cone step is specular).
+    One aperture per 8x8 block, twelve values on eight table keys (0.02, the 63- / 64- /
+    65-step apertures, 1.0, values clamping onto TAU_MIN / TAU_MAX, ...), traced three times:
+    each equals the oracle, whichever waves won the slots.  A second frame of twelve other
+    apertures then meets the full cache; a fresh context sees the frames in the other order;
+    both again with the tables off (0x100); and after another scene is voxelized in the first
+    context the tables (functions of tau, n and L only) still serve the first frame."""
+    from vct import scenes
+    from helpers import scene_arrays
+    first, second = TI.aperture_sets(32)
+    rig = Rig(oracle_mod, "cornell", 32, True, nd)
+    f1, f2 = _rough(rig, first), _rough(rig, second, 5)
+    r1, r2 = rig.oracle(f1), rig.oracle(f2)
+    assert (r1["steps_px"] != 0).mean() > 0.8
+    for k in range(3):
+        same(rig.host(f1), r1, f"nd {nd}: first frame, trace {k}")
+    same(rig.host(f2), r2, f"nd {nd}: second frame on a full cache")
+    same(rig.device(f2, REORDER, steps=False), r2, f"nd {nd}: second frame, reordered")
+    same(rig.host(f1), r1, f"nd {nd}: first frame again")
+    for v in (NO_TABLES, NO_TABLES | REORDER):
+        same(rig.device(f1, v), r1, f"nd {nd}: first frame, variant {v:#x}")
+        same(rig.device(f2, v), r2, f"nd {nd}: second frame, variant {v:#x}")
+    other = Rig(oracle_mod, "cornell", 32, True, nd)
+    same(other.host(f2), r2, f"nd {nd}: fresh context, second frame first")
+    same(other.host(f1), r1, f"nd {nd}: fresh context, first frame second")
+    other.close()
+    # D.5: another scene in the same context
+    _, arrays = scene_arrays("atrium")
+    rig.ctx.voxelize(*arrays)
+    rig.ctx.inject_directional(scenes.LIGHT_DIR, scenes.LIGHT_COLOR)
+    rig.ctx.build_mips()
+    rig.refresh()
+    ra = rig.oracle(f1)
+    assert not np.array_equal(ra["spec"], r1["spec"])
+    same(rig.host(f1), ra, f"nd {nd}: first frame after re-voxelizing the atrium")
+    same(rig.device(f1, UNION | SCREEN), ra, f"nd {nd}: ... union form")
+    rig.close()
+
+
+@pytest.mark.parametrize("n,tau,steps", [(32, "t63", 63), (32, "t64", 64), (32, "t65", 65), (32, 0.02, 89),
+                                         (16, 0.02, 54)])
+def test_table_step_counts(gpu_ready, oracle_mod, n, tau, steps):
+    """A march of exactly 63, 64, 65 (where `fits` flips), 89 and 54 steps: an empty grid and
+    the eye at 1e20 (a zero reflection: the cone stays at its origin, unobstructed, until
+    t > n sqrt3), no diffuse cones.  Every valid pixel whose origin lies in the grid takes the
+    CPU's count (tests/test_trace_inputs.py::test_aperture_step_counts); twice (the second
+    trace finds the table built), with the tables off, and reordered."""
+    from vct import Context, scenes
+    from vct.camera import Camera
+    import torch
+    tau = TI.tau_with_steps(steps, n) if isinstance(tau, str) else tau
+    assert TI.spec_steps(tau, n) == steps
+    g0, E = scenes.grid_for_unit_box(n)
+    rig = Rig.__new__(Rig)
+    rig.O, rig.n, rig.aniso, rig.nd, rig.specular, rig.g0, rig.E = oracle_mod, n, True, 0, True, g0, E
+    rig.ctx = Context(n, g0, E, aniso=True, n_diffuse=0, specular=True)
+    rig.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    rig.ctx.upload_level0(np.zeros((n, n, n, 4), F))
+    rig.ctx.build_mips()
+    rig.dev, rig.eye = torch.device("cuda"), TI.EYE_FAR
+    rig.refresh()
+    pos, nrm, alb = scenes.raycast_numpy(scenes.cornell(), Camera(), W, H)
+    alb = alb.copy()
+    alb[..., 3] = tau
+    gb = (pos, nrm, alb)
+    ref = rig.oracle(gb)
+    o = np.stack([TI.cone_origin(p, q, g0, E, n) for p, q in zip(pos.reshape(-1, 4), nrm.reshape(-1, 4))])
+    inside = ((o >= 0) & (o <= n)).all(-1).reshape(H, W) & (pos[..., 3] != 0)
+    assert inside.sum() > 1000 and (ref["steps_px"][inside] == steps).all() and not ref["steps_px"][~inside].any()
+    for k in range(2):
+        same(rig.host(gb), ref, f"n {n} tau {tau}: trace {k}")
+    for v in (NO_TABLES, REORDER, OCC | SCREEN, 1):
+        same(rig.device(gb, v), ref, f"n {n} tau {tau}: variant {v:#x}")
+    rig.close()
+
+
+@pytest.mark.parametrize("nd", [9, 0])
+def test_tables_broken_uniformity(gpu_ready, oracle_mod, nd):
+    """D.3: blocks where exactly one lane carries another aperture (lane 37, or the lowest
+    valid lane, whose tau the wave compares against), and a block half 63-step, half 64-step."""
+    t63, t64 = TI.tau_with_steps(63, 32), TI.tau_with_steps(64, 32)
+    rig = Rig(oracle_mod, "cornell", 32, True, nd)
+    pos, nrm, alb = rig.clean
+    alb = alb.copy()
+    alb[..., 3] = t63
+    valid = pos[..., 3] != 0
+    for by in range(H // 8):
+        for bx in range(W // 8):
+            kind = (by * (W // 8) + bx) % 4
+            blk = (slice(by * 8, by * 8 + 8), slice(bx * 8, bx * 8 + 8))
+            lanes = sorted(TI.lane_of(x, y) for y in range(8) for x in range(8) if valid[blk][y, x])
+            if kind == 1 or (kind == 2 and lanes):
+                mx, my = TI.lane_xy(37 if kind == 1 else lanes[0])
+                alb[by * 8 + my, bx * 8 + mx, 3] = t64
+            elif kind == 3:
+                for j in range(32, 64):
+                    mx, my = TI.lane_xy(j)
+                    alb[by * 8 + my, bx * 8 + mx, 3] = t64
+    gb = (pos, nrm, alb)
+    ref = rig.oracle(gb)
+    for k in range(2):
+        same(rig.host(gb), ref, f"nd {nd}: trace {k}")
+    for v in (UNION | SCREEN, OCC | SCREEN, NO_TABLES, REORDER):
+        same(rig.device(gb, v), ref, f"nd {nd}: variant {v:#x}")
+    rig.close()
+
+
+def test_tables_reordered_aperture_classes(gpu_ready, oracle_mod):
+    """D.4: G_rand positions and normals with a per-pixel roughness from the twelve-value
+    set, the frame the aperture-major specular key exists for: reordered (with the split
+    launch's specular order and without) and in screen order."""
+    from vct import scenes
+    first, _ = TI.aperture_sets(32)
+    rig = Rig(oracle_mod, "cornell", 32, True, 9)
+    pos, nrm, alb = scenes.gbuffer_rand(*rig.ctx.download_voxels(), rig.g0, rig.E, W, H, seed=42)
+    pos, nrm, alb = (np.asarray(a, F).reshape(H, W, 4) for a in (pos, nrm, alb))
+    alb = alb.copy()
+    alb[..., 3] = np.asarray(first, F)[np.random.default_rng(8).integers(0, 12, (H, W))]
+    gb = (pos, nrm, alb)
+    ref = rig.oracle(gb)
+    for k in range(2):
+        for v in (REORDER, SCREEN):
+            same(rig.device(gb, v, steps=False), ref, f"variant {v:#x}, split, trace {k}")
+            same(rig.device(gb, v), ref, f"variant {v:#x}, trace {k}")
+    same(rig.device(gb, REORDER | NO_TABLES, steps=False), ref, "reordered, tables off")
+    rig.close()
+
+
+@pytest.mark.parametrize("steps,table", [(63, True), (64, False), (65, False), (89, False)])
+def test_tables_path_counters(gpu_ready, oracle_mod, steps, table):
+    """D.7: which path ran, from the debug-counter build: a frame of a single aperture in the
+    n_diffuse = 0 context; on its second trace counter 36 counts table wave-steps and counter
+    38 per-lane wave-steps.  Only the 63-step march fits a 64-row table and its sentinel.
+
+    The debug library is loaded into this process beside the product one, as
+    test_exact_maps_skip_more does (no child process).  This is the only test that sees a
+    table one row short (spec_table's loop cut to 63 rows): such a table makes the 63-step
+    march fall back to per-lane steps, which give the same bits.  It skips without
+    vct/libvct_hip_dbg.so, so a GPU run that has not built `make dbg` does not guard the edge
+    where `fits` flips; test_table_step_counts still checks the results on both sides of it."""
+    import torch
+    from vct import Context, _lib, scenes
+    from vct.camera import Camera
+    path = os.path.join(os.path.dirname(_lib.LIB_PATH), "libvct_hip_dbg.so")
+    if not os.path.exists(path):
+        pytest.skip("no debug-counter library (make -C voxel-based-global-illumination_amd dbg)")
+    lib = _lib.bind(C.CDLL(path))
+    lib.vct_debug_counters.restype = C.c_int
+    lib.vct_debug_counters.argtypes = [C.c_void_p, C.c_int]
+    n = 32
+    tau = TI.tau_with_steps(steps, n) if steps != 89 else 0.02
+    assert TI.spec_steps(tau, n) == steps
+    s = scenes.cornell()
+    g0, E = scenes.grid_for_unit_box(n)
+    ctx = Context(n, g0, E, aniso=True, n_diffuse=0, specular=True, lib=lib)
+    ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    ctx.voxelize(*s.arrays())
+    ctx.inject_directional(scenes.LIGHT_DIR, scenes.LIGHT_COLOR)
+    ctx.build_mips()
+    cam = Camera()
+    pos, nrm, alb = scenes.raycast_numpy(s, cam, W, H)
+    alb = alb.copy()
+    alb[..., 3] = tau
+    ref = oracle_mod.trace(n, g0, E, ctx.download_level(0), gpu_pyramid_flat(ctx), pos, nrm, alb, cam.position,
+                           n_diffuse=0)
+    dev = torch.device("cuda")
+    gb = [torch.from_numpy(a).to(dev) for a in (pos, nrm, alb)]
+    d, sp = torch.empty((H, W, 4), device=dev), torch.empty((H, W, 4), device=dev)
+    ctr = (C.c_ulonglong * 56)()
+    for k in range(2):
+        torch.cuda.synchronize()
+        assert lib.vct_debug_counters(ctr, 1) == 0
+        ctx.trace_device(*gb, W, H, cam.position, d, sp, variant=UNION | SCREEN)
+        torch.cuda.synchronize()
+        assert lib.vct_debug_counters(ctr, 1) == 0
+        assert np.array_equal(d.cpu().numpy().view(np.uint32), ref["diffuse"].view(np.uint32))
+        assert np.array_equal(sp.cpu().numpy().view(np.uint32), ref["spec"].view(np.uint32))
+    c = list(ctr)                      # vct_debug_counters: counters 0..31, eight clocks, counters 32..47
+    tab, lane = c[40 + 36 - 32], c[40 + 38 - 32]
+    print(f"{steps}-step aperture {tau}: table wave-steps {tab}, per-lane wave-steps {lane}")
+    if table:
+        assert lane == 0 and tab > 0, (tab, lane)
+    else:
+        assert lane > 0 and tab == 0, (tab, lane)
+    ctx.close()
+
+
+# ---------------------------------------------------------------------------
+# E  the other consumers of the hostile frame
+# ---------------------------------------------------------------------------
+E_FAMILIES = ("position", "posw", "normal", "roughness")
+E_EXCLUDE = ("pos_big+", "pos_big-")        # see the module docstring
+
+
+def _consumer_setup(n=16):
+    """cornell at n on the GPU with light set S injected (lights_ref.cornell's scene and grid),
+    the hostile frame without the entries the references do not define, random finite
+    diffuse / specular inputs."""
+    import torch
+    import lights_ref
+    from vct import Context, scenes
+    from vct.camera import Camera
+    ref = lights_ref.cornell(n)
+    ctx = Context(n, ref["g0"], ref["E"])
+    ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    ctx.voxelize(*ref["arrays"])
+    ctx.inject_lights(ref["lights"])
+    ctx.build_mips()
+    clean = scenes.raycast_numpy(ref["scene"], Camera(), W, H)
+    fr = TI.build(clean, ref["g0"], ref["E"], n, E_FAMILIES, exclude=E_EXCLUDE)
+    placed = {w[0] for w in fr.where}
+    want = {e.name for e in TI.catalogue(ref["g0"], ref["E"], n) if e.family in E_FAMILIES} - set(E_EXCLUDE)
+    assert placed == want and len(want) == 47
+    assert np.isfinite(fr.pos[..., :3]).all() and np.isfinite(fr.nrm).all() and np.abs(fr.pos[..., :3]).max() < 1e5
+    dev = torch.device("cuda")
+    gb = [torch.from_numpy(a).to(dev) for a in (fr.pos, fr.nrm, fr.alb)]
+    gen = torch.Generator(device="cpu").manual_seed(3)
+    D = torch.rand((H, W, 4), generator=gen)
+    S = torch.rand((H, W, 4), generator=gen) * 0.2
+    return ctx, ref, fr, gb, D.to(dev), S.to(dev), D.numpy(), S.numpy()
+
+
+def _lin_same(got, want, fr, what):
+    d = (np.ascontiguousarray(got, F).view(np.uint32) != np.ascontiguousarray(want, F).view(np.uint32))
+    d = d.reshape(H, W, -1).any(-1)
+    ys, xs = np.nonzero(d)
+    names = [(int(y), int(x), fr.names[fr.entry[y, x]] if fr.entry[y, x] >= 0 else "clean")
+             for y, x in zip(ys[:12], xs[:12])]
+    assert not d.any(), f"{what}: {int(d.sum())} pixels differ, first: {names}"
+
+
+def test_consumer_composite(gpu_ready, oracle_mod):
+    """vct_composite_device on the hostile frame equals the oracle's composite (its shadow
+    walk starts at the same cone origin): linear output bit for bit, RGBA8 within 1 as in
+    test_composite_matches_oracle (powf differs by an ulp between libm and the device).
+    -0.0 in pos.w is background (the clear colour), 1e-45 and NaN are valid."""
+    import torch
+    from vct import scenes
+    ctx, ref, fr, gb, D, S, Dn, Sn = _consumer_setup()
+    lin = torch.empty((H, W, 4), device="cuda")
+    rgba = torch.empty((H, W), dtype=torch.int32, device="cuda")
+    ctx.composite_device(*gb, D, S, W, H, scenes.LIGHT_DIR, scenes.LIGHT_COLOR, out_linear4=lin, out_rgba8=rgba)
+    torch.cuda.synchronize()
+    ao, _ = ctx.download_voxels()
+    assert np.array_equal(ao.view(np.uint32), np.asarray(ref["grid"]["albedo_occ"], F).view(np.uint32))
+    want_lin, want_rgba = oracle_mod.composite(16, ref["g0"], ref["E"], ao, fr.pos, fr.nrm, fr.alb, Dn, Sn,
+                                               scenes.LIGHT_DIR, scenes.LIGHT_COLOR)
+    assert np.isfinite(want_lin).all()
+    _lin_same(lin.cpu().numpy(), want_lin, fr, "composite")
+    got = rgba.cpu().numpy().view(np.uint32)
+    for sh in (0, 8, 16, 24):
+        assert np.abs(((got >> sh) & 255).astype(np.int64) - ((want_rgba >> sh) & 255).astype(np.int64)).max() <= 1
+    for name, y, x in fr.where:
+        if name == "w_negzero":
+            assert want_lin[y, x, 3] == 0
+        elif name in ("w_denorm", "w_nan", "w_two", "w_negone"):
+            assert want_lin[y, x, 3] == 1
+    ctx.close()
+
+
+def test_consumer_composite_lights(gpu_ready, oracle_mod):
+    """vct_composite_lights_device with light set S on the hostile frame equals lights_ref."""
+    import torch
+    import lights_ref
+    ctx, ref, fr, gb, D, S, Dn, Sn = _consumer_setup()
+    lin = torch.empty((H, W, 4), device="cuda")
+    ctx.composite_lights_device(*gb, D, S, W, H, ref["lights"], out_linear4=lin)
+    torch.cuda.synchronize()
+    stats = []
+    want = lights_ref.composite(16, ref["g0"], ref["E"], ref["grid"]["albedo_occ"], fr.pos, fr.nrm, fr.alb, Dn, Sn,
+                                ref["lights"], stats)
+    assert np.isfinite(want).all() and all(s["walked"] for s in stats) and sum(s["blocked"] for s in stats) > 100
+    _lin_same(lin.cpu().numpy(), want, fr, "composite_lights")
+    ctx.close()
+
+
+def test_consumer_shadow_cones(gpu_ready, oracle_mod):
+    """vct_shadow_cones_device (seven soft lights and a hard one, shadow_ref's apertures) on
+    the hostile frame equals shadow_ref: every visibility plane bit for bit, and the steps."""
+    import torch
+    import shadow_ref
+    ctx, ref, fr, gb, D, S, Dn, Sn = _consumer_setup()
+    lights, tan_half = shadow_ref.lights_for(16), shadow_ref.TAN_HALF
+    vis = torch.full((len(lights), H, W), float("nan"), device="cuda")
+    steps = torch.zeros(1, dtype=torch.int64, device="cuda")
+    ctx.shadow_cones_device(gb[0], gb[1], W, H, lights, tan_half, vis, steps)
+    torch.cuda.synchronize()
+    want = shadow_ref.shadow(16, ref["g0"], ref["E"], ref["grid"]["albedo_occ"], shadow_ref.cornell_alpha(16), True,
+                             fr.pos, fr.nrm, lights, tan_half)
+    assert np.isfinite(want["vis"]).all() and want["steps"] > 0
+    got = vis.cpu().numpy()
+    for j in range(len(lights)):
+        _lin_same(got[j][..., None], want["vis"][j][..., None], fr, f"shadow plane {j}")
+    assert int(steps.item()) == want["steps"]
+    ctx.close()

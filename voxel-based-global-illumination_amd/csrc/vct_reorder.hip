@@ -158,7 +158,8 @@ __global__ void __launch_bounds__(256) k_reorder_count(const float4* __restrict_
         const float oz = (P.z - g0z) * inv_h + N.z;
         const auto q = [n, lk](float v) {
             const float f = floorf(v);
-            return (uint32_t)(f < 0.0f ? 0 : (f > (float)(n - 1) ? n - 1 : (int)f)) >> lk;
+            // !(f >= 0) also takes NaN, so the conversion only sees values in [0, n - 1]
+            return (uint32_t)(!(f >= 0.0f) ? 0 : (f > (float)(n - 1) ? n - 1 : (int)f)) >> lk;
         };
         c = spread3(q(ox)) | (spread3(q(oy)) << 1) | (spread3(q(oz)) << 2);
         const uint32_t cbits = 3u * (uint32_t)(__builtin_ctz((uint32_t)n) - lk);

@@ -1028,7 +1028,22 @@ template <bool O32, bool UNION, bool TAB, int KL, bool CNT = true>
 __device__ __forceinline__ uint32_t march_brick(const TraceK& k, bool valid, float ox, float oy, float oz,
                                                 float dx, float dy, float dz, float tau, float4& res,
                                                 uint32_t& texels, float4* __restrict__ lds, const StepRegs& tab,
-                                                PhaseClock& pc) {
+                                                PhaseClock& pc, bool chk_d) {
+    // A cone whose origin or direction has a non-finite component takes no step: at every
+    // t > 0 its position has a NaN or infinite component there, which the spec's inside
+    // test rejects (a finite o and d never give a NaN).  The min3 / max3 form of that test
+    // below skips a lone NaN, so such a lane is taken out before the march: k4_trace does
+    // it for the origin, once per pixel, and this does it for the direction.  The lane then
+    // counts as background for the wave's face union, shared direction and brick origins,
+    // and marches with d = 0 (o = 0): an inactive lane still samples (the branch-free
+    // compositing below), and a NaN position would give NaN weights and fmaf(+0, NaN, c).
+    // chk_d (wave-uniform): some lane's direction may be non-finite; k4_trace clears it for the
+    // diffuse cones of a wave whose normals are all small enough to rule that out.
+    if (chk_d) {
+        const bool dfin = __builtin_isfinite(dx) && __builtin_isfinite(dy) && __builtin_isfinite(dz);
+        valid = valid && dfin;
+        dx = dfin ? dx : 0.0f; dy = dfin ? dy : 0.0f; dz = dfin ? dz : 0.0f;
+    }
     const float tau2 = 2.0f * tau;
     const float nf = (float)k.n, Lf = (float)k.L;
     const int fx = dx >= 0.0f ? VCT_FACE_PX : VCT_FACE_NX;
@@ -1101,9 +1116,11 @@ __device__ __forceinline__ uint32_t march_brick(const TraceK& k, bool valid, flo
         }
         const float qx = ox + dx * t, qy = oy + dy * t, qz = oz + dz * t;
         // a >= 0.95, t > tmax or outside the grid ends the lane's march (no short-circuit
-        // branches).  Table rows end with t = +inf: q then has an infinite component (|d| = 1
-        // leaves at most two zero ones, whose NaN min3 / max3 skip), so `inside` already
-        // ends the march there and the t test is only needed for per-lane steps
+        // branches).  Table rows end with t = +inf: a component of q is then infinite where
+        // d's is nonzero and NaN where it is zero (o and d are finite here).  min3 / max3
+        // skip the NaNs beside an infinite one, and for d = 0 all three are NaN and both
+        // compares fail, so `inside` already ends the march there for any finite d (unit
+        // or not) and the t test is only needed for per-lane steps
         const float qmin = fminf(fminf(qx, qy), qz), qmax = fmaxf(fmaxf(qx, qy), qz);
         // one ballot per bare compare, ANDed as scalar masks (a ballot of an ANDed i1 goes
         // through a VGPR)
@@ -1300,9 +1317,21 @@ __global__ void __launch_bounds__(64, MINW) k4_trace(TraceK k) {
         float4 N4 = make_float4(0.0f, 1.0f, 0.0f, 0.0f);
         if (valid) N4 = k.nrm[pix];
         float nx = N4.x, ny = N4.y, nz = N4.z;
-        const float ox = (P.x - k.g0x) * k.inv_h + nx;
-        const float oy = (P.y - k.g0y) * k.inv_h + ny;
-        const float oz = (P.z - k.g0z) * k.inv_h + nz;
+        float ox = (P.x - k.g0x) * k.inv_h + nx;
+        float oy = (P.y - k.g0y) * k.inv_h + ny;
+        float oz = (P.z - k.g0z) * k.inv_h + nz;
+        // the brick marches take a lane whose cone origin is not finite out of the wave (see
+        // march_brick): no cone of such a pixel takes a step
+        bool mvalid = valid;
+        bool chk_diff = false;                   // wave-uniform: the diffuse directions need the finite test
+        if constexpr (BRICK) {
+            const bool ofin = __builtin_isfinite(ox) && __builtin_isfinite(oy) && __builtin_isfinite(oz);
+            mvalid = valid && ofin;
+            ox = ofin ? ox : 0.0f; oy = ofin ? oy : 0.0f; oz = ofin ? oz : 0.0f;
+            // every component of n below 1e9 in magnitude (a NaN fails the compare): |ka| <= 1, so
+            // the tangent frame stays below 1e18 + 1 and every diffuse d and d^2 is finite
+            chk_diff = !wall(fabsf(nx) < 1e9f && fabsf(ny) < 1e9f && fabsf(nz) < 1e9f);
+        }
         const float(*cones)[4] = cone_table(k.nd);
         for (int c = S3 ? c_lo : 0; c < c_hi; ++c) {
             // the tangent frame is rebuilt per cone (a few VALU per ~12 steps) instead of
@@ -1319,7 +1348,7 @@ __global__ void __launch_bounds__(64, MINW) k4_trace(TraceK k) {
             const float dy = (cn * ny + ct * Ty) + cb * By;
             const float dz = (cn * nz + ct * Tz) + cb * Bz;
             float4 res;
-            if constexpr (BRICK) steps += march_brick<O32, UNION, true, kKL, CNT>(k, valid, ox, oy, oz, dx, dy, dz, k.tau_d, res, texels, lds, tab, pc);
+            if constexpr (BRICK) steps += march_brick<O32, UNION, true, kKL, CNT>(k, mvalid, ox, oy, oz, dx, dy, dz, k.tau_d, res, texels, lds, tab, pc, chk_diff);
             else steps += march<O32>(k, ox, oy, oz, dx, dy, dz, k.tau_d, res, texels);
             if (S3 && grp >= 2) {                // later parts: results go to the hand-over scratch
                 if (in_frame || k.compact) st_coherent(&k.sc_cone[(size_t)(c - k.nd_chunk) * k.sc_px + oidx], res);
@@ -1351,9 +1380,9 @@ __global__ void __launch_bounds__(64, MINW) k4_trace(TraceK k) {
             float4 res;
             if constexpr (BRICK) {
                 if (spec_table(k, tau, wballot(valid), tab))
-                    steps += march_brick<O32, UNION, true, kKL, CNT>(k, valid, ox, oy, oz, rx, ry, rz, tau, res, texels, lds, tab, pc);
+                    steps += march_brick<O32, UNION, true, kKL, CNT>(k, mvalid, ox, oy, oz, rx, ry, rz, tau, res, texels, lds, tab, pc, true);
                 else
-                    steps += march_brick<O32, UNION, false, kKL, CNT>(k, valid, ox, oy, oz, rx, ry, rz, tau, res, texels, lds, tab, pc);
+                    steps += march_brick<O32, UNION, false, kKL, CNT>(k, mvalid, ox, oy, oz, rx, ry, rz, tau, res, texels, lds, tab, pc, true);
             } else {
                 steps += march<O32>(k, ox, oy, oz, rx, ry, rz, tau, res, texels);
             }
