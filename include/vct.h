@@ -152,7 +152,17 @@ uint32_t    vct_num_devices(const vct_ctx* ctx);   /* 1 for a vct_create context
  * per-triangle index into material_kd4 (NULL = material 0).  material_kd4:
  * n_materials x (Kd rgba) as in Material::Kd (material.h:10); NULL = white.
  * Replaces the previous voxel grid; the triangles are kept for
- * vct_gbuffer_raycast_device. */
+ * vct_gbuffer_raycast_device.
+ * Input rule (vct_spec.h "K1 input rule"), the same for every vct_voxelize* form:
+ *  - any finite vertex is legal, however far outside the grid (no candidates there);
+ *  - a triangle with a non-finite voxel-unit vertex component (NaN, +-Inf, or a finite
+ *    position whose (p - aabb_min) * n / extent overflows) is skipped: it covers no voxel
+ *    and no G-buffer ray hits it.  Not an error;
+ *  - the Kd.r, .g, .b of every material a triangle uses must be finite with |Kd| < 32768
+ *    (negative is legal).  Otherwise VCT_EINVAL ("material_kd4: Kd not finite or |Kd| >=
+ *    32768"), and the grid is refused afterwards exactly as after an index out of range:
+ *    inject, mips and trace return VCT_ESTATE until a voxelization succeeds.  The host forms
+ *    check this before any launch, the device forms in K1 itself. */
 vct_status vct_voxelize(vct_ctx* ctx, const void* verts, uint32_t vertex_stride, uint32_t n_verts,
                         const uint32_t* idx, uint32_t n_idx, const uint32_t* tri_material,
                         const float* material_kd4, uint32_t n_materials);

@@ -99,6 +99,22 @@
 /* ---- A.2 voxelization fixed point ------------------------------------------ */
 #define VCT_FIXED_ONE       65536.0f     /* round(x * 2^16) into int64 sums        */
 #define VCT_FIXED_ONE_D     65536.0
+/* K1 input rule (what a finite-or-not mesh means; every implementation restates it):
+ *  Candidate range of a triangle on one axis, from mn / mx = fminf / fmaxf of its three q:
+ *      lo = (int)ceilf(fminf(fmaxf(mn, -1), n + 1)) - 1,  clamped up to 0
+ *      hi = (int)floorf(fmaxf(fminf(mx, n + 1), -1)),     clamped down to n - 1
+ *    Both ends are clamped to [-1, n + 1] BEFORE the float -> int conversion, so the
+ *    conversion is defined for every finite q however far outside the grid.
+ *  Non-finite vertices: a triangle with any non-finite component of q (NaN or +-Inf; tested
+ *    on q, so an overflow of (p - g0) * inv_h counts) is skipped.  It has no candidates,
+ *    adds nothing to any voxel, and is kept for the G-buffer passes as an all-zero triangle
+ *    (zero origin and edges: no ray hits it).  It is not an error.
+ *  Kd: each of a triangle's material Kd.r, .g, .b must be finite with |Kd| < VCT_KD_LIMIT =
+ *    2^31 / VCT_FIXED_ONE: with a 32-bit count a voxel's int64 sum then cannot overflow,
+ *    and (int64)roundf(Kd * 2^16) is defined.  Otherwise the voxelization is an error
+ *    (VCT_EINVAL) and the grid is refused afterwards as for an index out of range.
+ *    Negative finite Kd is legal.  Kd.a is not read. */
+#define VCT_KD_LIMIT        32768.0f
 
 /* ---- diffuse maps (albedo = Kd x diffuse map; SURVEY 8a Model::loadMaterials) --
  * The reference loads a material's map_Kd with stbi_load(path, .., 0), uploads it

@@ -110,6 +110,8 @@ def voxelize(n, aabb_min, extent, verts, idx, tri_mat=None, kd4=None, mat_map=No
     rc = lib().vo_voxelize_tex(n, _p(g0), C.c_float(extent), _p(verts), verts.shape[1] * 4, verts.shape[0],
                                _p(idx), idx.size, _p(mat), _p(kd), n_mat, _p(mm), uv_offset,
                                C.cast(tarr, C.c_void_p), len(keep), _p(sums), _p(counts))
+    if rc == -2:
+        raise ValueError("oracle voxelize: Kd not finite or |Kd| >= 32768")
     if rc != 0:
         raise ValueError("oracle voxelize: index out of range")
     return sums, counts

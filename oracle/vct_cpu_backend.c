@@ -159,7 +159,7 @@ static vct_status voxelize_common(vct_ctx* c, const void* verts, uint32_t stride
     if (map) c->uv = (float*)calloc((size_t)(n_tri ? n_tri : 1) * 6, sizeof(float));
     if (!c->tri || (map && !c->uv)) return fail(c, VCT_ENOMEM, "mesh records");
     c->n_tri = n_tri;
-    int bad = 0;
+    int bad = 0, bad_kd = 0;
     for (uint32_t t = 0; t < n_tri; ++t) {
         const uint32_t vi[3] = {idx[3 * t], idx[3 * t + 1], idx[3 * t + 2]};
         const uint32_t m = tri_mat ? tri_mat[t] : 0u;
@@ -171,10 +171,27 @@ static vct_status voxelize_common(vct_ctx* c, const void* verts, uint32_t stride
         const float* p1 = (const float*)((const char*)verts + (size_t)vi[1] * stride);
         const float* p2 = (const float*)((const char*)verts + (size_t)vi[2] * stride);
         float* r = c->tri + (size_t)t * 16;
+        r[12] = kd4 ? kd4[4 * m] : 1.0f; r[13] = kd4 ? kd4[4 * m + 1] : 1.0f; r[14] = kd4 ? kd4[4 * m + 2] : 1.0f;
+        if (!(fabsf(r[12]) < VCT_KD_LIMIT && fabsf(r[13]) < VCT_KD_LIMIT && fabsf(r[14]) < VCT_KD_LIMIT)) {
+            bad_kd = 1;
+            continue;
+        }
+        {   /* a triangle with a non-finite q is skipped (vct_spec.h "K1 input rule"): an all-zero
+             * record (calloc) that no G-buffer ray hits */
+            const float inv_h = (float)c->n / c->cfg.extent;
+            int finite = 1;
+            const float* pk[3] = {p0, p1, p2};
+            for (int k = 0; k < 3; ++k)
+                for (int a = 0; a < 3; ++a) finite &= isfinite((pk[k][a] - c->cfg.aabb_min[a]) * inv_h);
+            if (!finite) {
+                const int32_t none = -1;
+                memcpy(r + 15, &none, 4);
+                continue;
+            }
+        }
         r[0] = p0[0]; r[1] = p0[1]; r[2] = p0[2];
         r[4] = p1[0] - p0[0]; r[5] = p1[1] - p0[1]; r[6] = p1[2] - p0[2];
         r[8] = p2[0] - p0[0]; r[9] = p2[1] - p0[1]; r[10] = p2[2] - p0[2];
-        r[12] = kd4 ? kd4[4 * m] : 1.0f; r[13] = kd4 ? kd4[4 * m + 1] : 1.0f; r[14] = kd4 ? kd4[4 * m + 2] : 1.0f;
         const int32_t tex = map ? map[m] : -1;
         memcpy(r + 15, &tex, 4);
         if (tex >= 0)
@@ -182,12 +199,14 @@ static vct_status voxelize_common(vct_ctx* c, const void* verts, uint32_t stride
                 memcpy(c->uv + (size_t)t * 6 + 2 * k,
                        (const char*)verts + (size_t)vi[k] * stride + uv_offset, 8);
     }
-    if (n_idx && vo_voxelize_tex(c->n, c->cfg.aabb_min, c->cfg.extent, verts, stride, n_verts, idx, n_idx, tri_mat,
-                                 kd4, n_mat, map, uv_offset, c->tex, c->n_tex, c->sums, c->counts) != 0)
+    if (n_idx && !bad_kd &&
+        vo_voxelize_tex(c->n, c->cfg.aabb_min, c->cfg.extent, verts, stride, n_verts, idx, n_idx, tri_mat,
+                        kd4, n_mat, map, uv_offset, c->tex, c->n_tex, c->sums, c->counts) != 0)
         bad = 1;
     vo_resolve(c->n, c->sums, c->counts, c->albedo_occ, c->normal);
-    c->voxelized = !bad;     /* a partial grid (bad indices) is refused by inject / mips / trace */
+    c->voxelized = !bad && !bad_kd;   /* a partial grid (bad indices, an illegal Kd) is refused by inject / mips / trace */
     c->injected = c->mipped = 0;
+    if (bad_kd) return fail(c, VCT_EINVAL, "material_kd4: Kd not finite or |Kd| >= 32768");
     if (bad) return fail(c, VCT_EINVAL, "vertex, material or diffuse-map index out of range");
     return VCT_OK;
 }

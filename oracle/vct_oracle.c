@@ -91,9 +91,11 @@ static int tri_box_overlap(v3 q0, v3 q1, v3 q2, v3 c) {
     return 1;
 }
 
+/* vct_spec.h "K1 input rule": both ends clamped to [-1, n + 1] before the conversion */
 static void cand_range(float mn, float mx, uint32_t n, int* lo, int* hi) {
-    int l = (int)ceilf(fmaxf(mn, -1.0f)) - 1;
-    int h = (int)floorf(fminf(mx, (float)n + 1.0f));
+    const float top = (float)n + 1.0f;
+    int l = (int)ceilf(fminf(fmaxf(mn, -1.0f), top)) - 1;
+    int h = (int)floorf(fmaxf(fminf(mx, top), -1.0f));
     if (l < 0) l = 0;
     if (h > (int)n - 1) h = (int)n - 1;
     *lo = l; *hi = h;
@@ -167,8 +169,14 @@ int vo_voxelize_tex(uint32_t n, const float g0[3], float extent,
         if ((kd4 || mat_map) && mat >= n_mat) return -1;
         const int32_t map = mat_map ? mat_map[mat] : -1;
         if (map < -1 || (map >= 0 && (uint32_t)map >= n_tex)) return -1;
+        float kd[3];
+        for (int c = 0; c < 3; ++c) {   /* Kd rule: finite, |Kd| < VCT_KD_LIMIT (NaN fails the compare) */
+            kd[c] = kd4 ? kd4[4 * mat + c] : 1.0f;
+            if (!(fabsf(kd[c]) < VCT_KD_LIMIT)) return -2;
+        }
         v3 p[3], q[3];
         float uv[6] = {0, 0, 0, 0, 0, 0};
+        int finite = 1;
         for (int k = 0; k < 3; ++k) {
             const char* rec = (const char*)verts + (size_t)vi[k] * stride;
             const float* f = (const float*)rec;
@@ -176,19 +184,17 @@ int vo_voxelize_tex(uint32_t n, const float g0[3], float extent,
             q[k].x = (p[k].x - g0[0]) * inv_h;
             q[k].y = (p[k].y - g0[1]) * inv_h;
             q[k].z = (p[k].z - g0[2]) * inv_h;
+            finite &= isfinite(q[k].x) && isfinite(q[k].y) && isfinite(q[k].z);
             if (map >= 0) memcpy(uv + 2 * k, rec + uv_offset, 8);
         }
+        if (!finite) continue;   /* a non-finite q: the triangle is skipped */
         /* face normal (world units) and albedo in 16.16 fixed point */
         v3 fn = v3cross(v3sub(p[1], p[0]), v3sub(p[2], p[0]));
         float len = sqrtf(v3dot(fn, fn));
         if (len > 0.0f) { fn.x = fn.x / len; fn.y = fn.y / len; fn.z = fn.z / len; }
         else { fn.x = 0.0f; fn.y = 0.0f; fn.z = 0.0f; }
         int64_t fix[6];
-        float kd[3];
-        for (int c = 0; c < 3; ++c) {
-            kd[c] = kd4 ? kd4[4 * mat + c] : 1.0f;
-            fix[c] = (int64_t)roundf(kd[c] * VCT_FIXED_ONE);
-        }
+        for (int c = 0; c < 3; ++c) fix[c] = (int64_t)roundf(kd[c] * VCT_FIXED_ONE);
         fix[3] = (int64_t)roundf(fn.x * VCT_FIXED_ONE);
         fix[4] = (int64_t)roundf(fn.y * VCT_FIXED_ONE);
         fix[5] = (int64_t)roundf(fn.z * VCT_FIXED_ONE);

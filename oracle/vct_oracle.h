@@ -38,7 +38,9 @@ size_t vo_level_offset(uint32_t n, int aniso, uint32_t level);
 /* K1 (A.2): conservative SAT voxelization into fixed-point sums.
  * pos: vertex positions, vertex i at (const char*)verts + i*stride (3 floats).
  * sums6: [n^3][6] int64 (albedo rgb, normal xyz), counts: [n^3] uint32.
- * Arrays are accumulated into (caller zeroes them).  Returns 0 / -1 on bad index. */
+ * Arrays are accumulated into (caller zeroes them).  Returns 0 / -1 on bad index /
+ * -2 on a Kd that is not finite or not below VCT_KD_LIMIT in magnitude.  A triangle with a
+ * non-finite voxel-unit vertex is skipped (vct_spec.h "K1 input rule"). */
 int vo_voxelize(uint32_t n, const float g0[3], float extent,
                 const void* verts, uint32_t stride, uint32_t n_verts,
                 const uint32_t* idx, uint32_t n_idx,
@@ -64,7 +66,7 @@ void vo_tri_uv(const float uv6[6], float b1, float b2, float* u, float* v);
 /* K1 with diffuse maps: material m's triangles (mat_map[m] >= 0) contribute
  * albedo = Kd x T(uv at the voxel centre's projection) per covered voxel; UVs are
  * the two floats at byte uv_offset of each vertex record.  mat_map NULL = vo_voxelize.
- * Returns -1 on a bad vertex / material / texture index. */
+ * Returns -1 on a bad vertex / material / texture index, -2 on an illegal Kd. */
 int vo_voxelize_tex(uint32_t n, const float g0[3], float extent,
                     const void* verts, uint32_t stride, uint32_t n_verts,
                     const uint32_t* idx, uint32_t n_idx,

@@ -208,21 +208,27 @@ def voxelize(n, g0, extent, verts, idx, tri_mat=None, kd4=None, mat_map=None, te
     counts = np.zeros(n ** 3, np.int64)
     idx = np.asarray(idx).reshape(-1, 3)
     for t, tri in enumerate(idx):
+        m = 0 if tri_mat is None else int(tri_mat[t])
+        kd = np.ones(3, F) if kd4 is None else np.asarray(kd4, F)[m, :3]
+        if not (np.abs(kd) < F(32768)).all():   # Kd rule (vct_spec.h "K1 input rule"); NaN fails
+            raise ValueError("spec_ref voxelize: Kd not finite or |Kd| >= 32768")
         p = np.asarray(verts, F)[tri, :3]
-        q = (p - g0) * inv_h
+        with np.errstate(all="ignore"):
+            q = (p - g0) * inv_h
+        if not np.isfinite(q).all():            # a non-finite q: the triangle is skipped
+            continue
         e1, e2 = p[1] - p[0], p[2] - p[0]
         fn = np.array([e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2],
                        e1[0] * e2[1] - e1[1] * e2[0]], F)
         ln = np.sqrt(_dot(*fn, *fn))
         fn = fn / ln if ln > 0 else np.zeros(3, F)
-        m = 0 if tri_mat is None else int(tri_mat[t])
-        kd = np.ones(3, F) if kd4 is None else np.asarray(kd4, F)[m, :3]
         fix = np.concatenate([_roundf(kd * F(65536)), _roundf(fn * F(65536))])
         lo, hi = [], []
         for a in range(3):
             mn, mx = np.fmin(np.fmin(q[0, a], q[1, a]), q[2, a]), np.fmax(np.fmax(q[0, a], q[1, a]), q[2, a])
-            lo.append(max(0, int(np.ceil(np.fmax(mn, F(-1)))) - 1))
-            hi.append(min(n - 1, int(np.floor(np.fmin(mx, F(n) + F(1))))))
+            top = F(n) + F(1)               # both ends clamped to [-1, n + 1] before the conversion
+            lo.append(max(0, int(np.ceil(np.fmin(np.fmax(mn, F(-1)), top))) - 1))
+            hi.append(min(n - 1, int(np.floor(np.fmax(np.fmin(mx, top), F(-1))))))
         if any(l > h for l, h in zip(lo, hi)):
             continue
         zz, yy, xx = np.meshgrid(*[np.arange(lo[a], hi[a] + 1) for a in (2, 1, 0)], indexing="ij")

@@ -389,7 +389,9 @@ static vct_status voxelize_args(vct_ctx* c, const void* verts, uint32_t stride, 
     return use_device(c);
 }
 
-// K1 on device-resident geometry; `derr` (device int) receives the index-range flag.
+static const char* const kKdMessage = "material_kd4: Kd not finite or |Kd| >= 32768";
+
+// K1 on device-resident geometry; `derr` (device int) receives the index-range and Kd flags.
 // dmap (device, may be NULL): each material's diffuse map (vct_voxelize_textured).
 static vct_status voxelize_dev(vct_ctx* c, const void* dv, uint32_t stride, uint32_t n_verts, const uint32_t* di,
                                uint32_t n_tri, const uint32_t* dm, const float4* dk, uint32_t n_mat,
@@ -434,9 +436,11 @@ static vct_status voxelize_dev(vct_ctx* c, const void* dv, uint32_t stride, uint
         VCT_HIP(hipMemcpyAsync(&herr, derr, 4, hipMemcpyDeviceToHost, c->stream), "download err");
         VCT_HIP(hipStreamSynchronize(c->stream), "voxelize sync");
         // a pass whose packed sums may have overflowed is repeated with the seven-atomic form
-        if ((herr & kK1ErrIndex) || !(herr & kK1ErrRedo)) break;
+        if ((herr & (kK1ErrIndex | kK1ErrKd)) || !(herr & kK1ErrRedo)) break;
     }
-    // a grid from out-of-range indices is partial: inject / mips / trace refuse it (VCT_ESTATE)
+    // a grid from out-of-range indices or an illegal Kd is partial: inject / mips / trace
+    // refuse it (VCT_ESTATE)
+    if (herr & kK1ErrKd) return fail(c, VCT_EINVAL, kKdMessage);
     if (herr & kK1ErrIndex) return fail(c, VCT_EINVAL, "vertex, material or diffuse-map index out of range");
     g.voxelized = true;
     return VCT_OK;
@@ -463,6 +467,23 @@ static vct_status voxelize_host(vct_ctx* c, const void* verts, uint32_t stride, 
                                                " is not a texture of vct_set_textures (" + std::to_string(c->tex.n) +
                                                " set) or -1");
     const uint32_t n_tri = n_idx / 3;
+    // the Kd rule (vct_spec.h "K1 input rule"), on the host before any launch: the Kd of every
+    // material a triangle uses (an out-of-range material index is K1's to report).  The
+    // previous grid is refused from here on, as after a failed K1
+    if (kd4)
+        for (uint32_t t = 0; t < n_tri; ++t) {
+            const uint32_t m = tri_mat ? tri_mat[t] : 0u;
+            if (m >= n_mat) continue;
+            const float* k = kd4 + 4 * (size_t)m;
+            if (!(fabsf(k[0]) < VCT_KD_LIMIT && fabsf(k[1]) < VCT_KD_LIMIT && fabsf(k[2]) < VCT_KD_LIMIT)) {
+                Grid& g = c->grid;
+                g.voxelized = g.injected = g.mipped = g.bounced = false;
+                g.k2_coarse_ok = g.k3_sparse_ok = g.zm_valid = false;
+                g.k3_live_bz = 0;
+                ++c->grid_epoch;
+                return fail(c, VCT_EINVAL, kKdMessage);
+            }
+        }
     // host -> device staging (the reference keeps CPU copies of vertices / indices
     // next to its GL buffers, mesh.h:17-18; this is the same one-time upload)
     DeviceBuf dv, di, dm, dk, dmap, derr;

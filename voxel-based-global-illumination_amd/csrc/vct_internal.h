@@ -277,10 +277,11 @@ namespace vct {
 // K1
 // d_map (device, n_mat entries, may be NULL): diffuse map of each material in c->tex
 // (-1 none); uv_offset: byte offset of the TexCoords in a vertex record (read when d_map).
-// *d_err (device, zeroed by the caller) collects kK1ErrIndex (an index out of range) and
+// *d_err (device, zeroed by the caller) collects kK1ErrIndex (an index out of range),
+// kK1ErrKd (a triangle's Kd is not finite or |Kd| >= VCT_KD_LIMIT) and
 // kK1ErrRedo (packed sums may have overflowed: repeat with packed = false); nothing is
 // read back here, so the launch queues without a synchronisation after the candidate count.
-constexpr int kK1ErrIndex = 1, kK1ErrRedo = 2;
+constexpr int kK1ErrIndex = 1, kK1ErrRedo = 2, kK1ErrKd = 4;
 hipError_t launch_voxelize(vct_ctx* c, const void* d_verts,
                            uint32_t stride, uint32_t n_verts, const uint32_t* d_idx, uint32_t n_tri,
                            const uint32_t* d_mat, const float4* d_kd, uint32_t n_mat, const int32_t* d_map,

@@ -60,9 +60,11 @@ struct TriUV {        // 48 B, textured triangles only
 __device__ __forceinline__ float fmin3(float a, float b, float c) { return fminf(fminf(a, b), c); }
 __device__ __forceinline__ float fmax3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
 
+// vct_spec.h "K1 input rule": both ends clamped to [-1, n + 1] before the conversion
 __device__ __forceinline__ void cand_range(float mn, float mx, int n, int& lo, int& hi) {
-    int l = (int)ceilf(fmaxf(mn, -1.0f)) - 1;
-    int h = (int)floorf(fminf(mx, (float)n + 1.0f));
+    const float top = (float)n + 1.0f;
+    int l = (int)ceilf(fminf(fmaxf(mn, -1.0f), top)) - 1;
+    int h = (int)floorf(fmaxf(fminf(mx, top), -1.0f));
     lo = l < 0 ? 0 : l;
     hi = h > n - 1 ? n - 1 : h;
 }
@@ -91,6 +93,10 @@ __global__ void __launch_bounds__(256) k1_tri_setup(
         geom[t] = g;
         return;
     }
+    // the K1 input rule (vct_spec.h): Kd outside the fixed-point range is an error, a triangle with
+    // a non-finite q is skipped (NaN fails both compares).  Tested after the vertex loads, so
+    // that all of them are in flight together
+    const float4 alb = kd ? kd[m] : make_float4(1.0f, 1.0f, 1.0f, 1.0f);
     float p[3][3], q[3][3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -101,6 +107,28 @@ __global__ void __launch_bounds__(256) k1_tri_setup(
         q[k][2] = (p[k][2] - g0z) * inv_h;
         g.q[3 * k] = q[k][0]; g.q[3 * k + 1] = q[k][1]; g.q[3 * k + 2] = q[k][2];
     }
+    // (`&`, not `&&`: short-circuit evaluation would make each load wait for the one before it)
+    const bool kd_ok = (fabsf(alb.x) < VCT_KD_LIMIT) & (fabsf(alb.y) < VCT_KD_LIMIT) & (fabsf(alb.z) < VCT_KD_LIMIT);
+    bool finite = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        finite &= (fabsf(q[k][0]) < __builtin_inff()) & (fabsf(q[k][1]) < __builtin_inff()) &
+                  (fabsf(q[k][2]) < __builtin_inff());
+    if (!kd_ok || !finite) {   // no candidates, nothing for max|value|, a zero triangle for the G-buffer passes
+        if (!kd_ok) atomicOr(err, kK1ErrKd);
+        g.lo[0] = g.lo[1] = g.lo[2] = 0;
+        g.ext[0] = g.ext[1] = g.ext[2] = 0;
+        g.pad = 0;
+        geom[t] = g;
+        counts[t] = 0;
+        const float4 z4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        mesh_tri[4 * t + 0] = z4;
+        mesh_tri[4 * t + 1] = z4;
+        mesh_tri[4 * t + 2] = z4;
+        mesh_tri[4 * t + 3] = make_float4(alb.x, alb.y, alb.z, __int_as_float(-1));
+        if (tex >= 0) { mesh_uv[2 * t + 0] = z4; mesh_uv[2 * t + 1] = z4; }
+        return;
+    }
     float e1[3] = {p[1][0] - p[0][0], p[1][1] - p[0][1], p[1][2] - p[0][2]};
     float e2[3] = {p[2][0] - p[0][0], p[2][1] - p[0][1], p[2][2] - p[0][2]};
     float fn[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2],
@@ -108,7 +136,6 @@ __global__ void __launch_bounds__(256) k1_tri_setup(
     float len = sqrtf(dot3(fn[0], fn[1], fn[2], fn[0], fn[1], fn[2]));
     if (len > 0.0f) { fn[0] = fn[0] / len; fn[1] = fn[1] / len; fn[2] = fn[2] / len; }
     else { fn[0] = 0.0f; fn[1] = 0.0f; fn[2] = 0.0f; }
-    float4 alb = kd ? kd[m] : make_float4(1.0f, 1.0f, 1.0f, 1.0f);
     f.fix[0] = (long long)roundf(alb.x * VCT_FIXED_ONE);
     f.fix[1] = (long long)roundf(alb.y * VCT_FIXED_ONE);
     f.fix[2] = (long long)roundf(alb.z * VCT_FIXED_ONE);
