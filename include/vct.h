@@ -206,7 +206,11 @@ vct_status vct_voxelize_textured_device(vct_ctx* ctx, const void* verts, uint32_
                                         const float* material_kd4, const int32_t* material_map,
                                         uint32_t n_materials, uint32_t uv_offset);
 
-/* ---- K2 direct-light injection (A.3) ----------------------------------- */
+/* ---- K2 direct-light injection (A.3) -----------------------------------
+ * Input rule (vct_spec.h "K2 input rule"), also vct_composite_device's: the float32 length of
+ * dir_to_light must be finite and > 0 (a squared length that underflows to 0 or overflows is
+ * refused); each colour component must be finite, not negative (-0.0f included) and
+ * <= VCT_COLOR_LIMIT.  Otherwise VCT_EINVAL, and level 0 stays as it was. */
 vct_status vct_inject_directional(vct_ctx* ctx, const float dir_to_light[3], const float color[3]);
 
 /* ---- K3 mip build (A.4) --------------------------------------------------- */

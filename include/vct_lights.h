@@ -37,7 +37,7 @@ typedef struct vct_light {      /* 60 bytes, host memory */
     float position[3];   /* world; point, spot                                         */
     float direction[3];  /* directional: toward the light (as vct_inject_directional);
                             spot: the axis the spot shines along (away from the light) */
-    float color[3];      /* finite, >= 0                                               */
+    float color[3];      /* finite, >= 0 (not -0.0f), <= VCT_COLOR_LIMIT (vct_spec.h)  */
     float range;         /* world units, > 0; point, spot: no light at distance >= range */
     float cos_inner;     /* spot: full intensity inside, 1 >= cos_inner > cos_outer >= 0 */
     float cos_outer;     /* spot: no light outside                                     */
@@ -52,7 +52,8 @@ typedef struct vct_light {      /* 60 bytes, host memory */
  * a point light's direction and cosines) are ignored but must be finite.
  * VCT_ESTATE before a voxelization.  VCT_EINVAL, with nothing changed: NULL lights with
  * n_lights > 0, n_lights > VCT_MAX_LIGHTS, an unknown type, a non-finite field, a negative
- * colour, a zero direction where one is used, range <= 0 (point, spot), cosines that break
+ * colour or one above VCT_COLOR_LIMIT, a direction whose float32 length is not finite and > 0
+ * where one is used (vct_spec.h "K2 input rule"), range <= 0 (point, spot), cosines that break
  * 1 >= cos_inner > cos_outer >= 0 (spot), nonzero reserved words.
  * Queued on the ctx stream; never waits for the device.  On a vct_create_multi context
  * device 0 injects; the result reaches the other devices with vct_build_mips. */

@@ -116,6 +116,30 @@
  *    Negative finite Kd is legal.  Kd.a is not read. */
 #define VCT_KD_LIMIT        32768.0f
 
+/* K2 input rule (what a light direction and colour mean to the A.3 shadow walk, to
+ * vct_inject_directional, vct_composite_device and every light of a list; every implementation
+ * restates it):
+ *  Direction: len = sqrtf((dx*dx + dy*dy) + dz*dz) in float32 must be finite and > 0, otherwise
+ *    the call is an error (VCT_EINVAL).  A non-finite component is therefore refused, and so is
+ *    a finite direction whose squared length underflows to 0 or overflows to +inf.  l = d / len
+ *    per component (directional lights, and the axis of a spot light).
+ *  Walk: per axis a, s_a = sign(l_a) and td_a = 1.0f / fabsf(l_a) (+inf where l_a == 0).  An
+ *    axis whose td_a is not finite does not move: s_a = 0 and tm_a = +inf.  That is the axis of
+ *    a zero component, as always, and now also of a component with |l_a| <= 2^-128 (a denormal
+ *    whose reciprocal overflows), for which (q_a - v_a) * td_a would be 0 * inf = NaN at an
+ *    integer q_a.  Under this rule no t of the walk is ever NaN: tm_a starts as a finite
+ *    non-negative product or +inf, and only grows by additions of a positive td_a.  The step is
+ *    x if tmx <= tmy and tmx <= tmz, else y if tmy <= tmz, else z; at least one component of l
+ *    is O(1), so the axis chosen always has a finite t.
+ *  Colour: each of color.r, .g, .b must be finite, not negative (-0.0f counts as negative, by
+ *    its sign bit) and <= VCT_COLOR_LIMIT, otherwise VCT_EINVAL.  An error leaves level 0 as it
+ *    was.  The limit keeps level 0 finite: a voxel's albedo is an average of legal Kd x T, so
+ *    |A| < VCT_KD_LIMIT = 2^15; ndl <= |N| |l| plus rounding < 2 for a unit normal; f <= 1 and
+ *    V <= 1; at most VCT_MAX_LIGHTS = 2^6 lights are summed.  With color <= 2^105 every
+ *    contribution is below 2^15 * 2^105 * 2 = 2^121 and the sum below 2^127 < FLT_MAX:
+ *    VCT_COLOR_LIMIT = 2^127 / (VCT_KD_LIMIT * 2 * VCT_MAX_LIGHTS) = 2^105. */
+#define VCT_COLOR_LIMIT     4.05648192e31f   /* 2^105 exactly */
+
 /* ---- diffuse maps (albedo = Kd x diffuse map; SURVEY 8a Model::loadMaterials) --
  * The reference loads a material's map_Kd with stbi_load(path, .., 0), uploads it
  * as glTexImage2D(GL_RED | GL_RGB | GL_RGBA, GL_UNSIGNED_BYTE) and samples it with
@@ -214,7 +238,8 @@
  *    ndl = dot3(N, l);  the light is skipped unless ndl > 0 and f > 0.
  *  (f is the physical 1 / (1 + r_world^2) falloff under a window that reaches zero, with a
  *  zero slope, at r_world = range.)
- *  Visibility V: the A.3 shadow walk (vct_device.h dda_visibility) from q along l, cell
+ *  Visibility V: the A.3 shadow walk (vct_device.h dda_visibility; "K2 input rule": an axis
+ *  whose td is not finite does not move) from q along l, cell
  *  for cell, with one more end.  t_e is the t at which the current cell was entered: 0 for
  *  the first cell; after a step, the tm value that was the minimum chosen (before td is
  *  added to it).  Before a cell is tested: t_e >= t_lim gives V = 1 (the light is

@@ -265,11 +265,26 @@ vct_status vct_set_textures(vct_ctx* c, const vct_texture* t, uint32_t n) {
 }
 
 /* ---- K2 / K3 ---------------------------------------------------------------- */
+/* K2 input rule (vct_spec.h).  Direction: len in float32 finite and > 0 (a squared length that
+ * underflows to 0 or overflows to +inf is refused).  Colour: finite, not negative (-0.0f by its
+ * sign bit) and <= VCT_COLOR_LIMIT, which keeps level 0 finite.  An error leaves level 0 as it
+ * was.  The walk's part of the rule is dda_visibility's (vct_oracle.c). */
+static const char* bad_light(const float dir[3], const float color[3]) {
+    const float len = sqrtf((dir[0] * dir[0] + dir[1] * dir[1]) + dir[2] * dir[2]);
+    if (!(len > 0.0f) || !isfinite(len)) return "zero or non-finite light direction";
+    for (int k = 0; k < 3; ++k) {
+        if (!isfinite(color[k])) return "non-finite colour";
+        if (!(color[k] >= 0.0f) || signbit(color[k])) return "negative colour";
+        if (color[k] > VCT_COLOR_LIMIT) return "colour above VCT_COLOR_LIMIT";
+    }
+    return NULL;
+}
+
 vct_status vct_inject_directional(vct_ctx* c, const float dir[3], const float color[3]) {
     if (!c || !dir || !color) return VCT_EINVAL;
     if (!c->voxelized) return fail(c, VCT_ESTATE, "inject before voxelize");
-    const float len = sqrtf((dir[0] * dir[0] + dir[1] * dir[1]) + dir[2] * dir[2]);
-    if (!(len > 0.0f) || !isfinite(len)) return fail(c, VCT_EINVAL, "zero or non-finite light direction");
+    const char* bad = bad_light(dir, color);
+    if (bad) return fail(c, VCT_EINVAL, bad);
     vo_inject(c->n, c->albedo_occ, c->normal, dir, color, c->r0);
     c->injected = 1;
     c->mipped = 0;
@@ -596,9 +611,8 @@ vct_status vct_composite_device(vct_ctx* c, const float* pos4, const float* nrm4
         return VCT_EINVAL;
     if (!out_linear4 && !out_rgba8) return fail(c, VCT_EINVAL, "composite: no output");
     if (!c->voxelized) return fail(c, VCT_ESTATE, "composite before voxelize");
-    const float len = sqrtf((dir_to_light[0] * dir_to_light[0] + dir_to_light[1] * dir_to_light[1]) +
-                            dir_to_light[2] * dir_to_light[2]);
-    if (!(len > 0.0f) || !isfinite(len)) return fail(c, VCT_EINVAL, "zero or non-finite light direction");
+    const char* bad = bad_light(dir_to_light, color);   /* K2 input rule, as vct_inject_directional */
+    if (bad) return fail(c, VCT_EINVAL, bad);
     vo_composite(c->n, c->cfg.aabb_min, c->cfg.extent, c->albedo_occ, pos4, nrm4, alb4, diffuse4, spec4, w, h,
                  dir_to_light, color, out_linear4, out_rgba8);
     return VCT_OK;

@@ -274,7 +274,11 @@ static int occupied(const float* albedo_occ4, uint32_t n, int x, int y, int z) {
     return albedo_occ4[4 * v + 3] != 0.0f;
 }
 
-/* Amanatides-Woo voxel walk from q (voxel units) along l.  1 = reaches outside. */
+/* Amanatides-Woo voxel walk from q (voxel units) along l.  1 = reaches outside.
+ * K2 input rule (vct_spec.h): an axis whose td is not finite -- l_a == 0, or |l_a| <= 2^-128,
+ * whose reciprocal overflows -- does not move (s_a = 0, tm_a = +inf), so no t is ever NaN.
+ * l must be legal by that rule (unit length to rounding; vct_cpu_backend.c checks it before
+ * vo_inject / vo_composite): a walk along a vector without any finite td would never end. */
 static float dda_visibility(const float* albedo_occ4, uint32_t n, v3 q, v3 l) {
     int vx = (int)floorf(q.x), vy = (int)floorf(q.y), vz = (int)floorf(q.z);
     const int N = (int)n;
@@ -285,6 +289,9 @@ static float dda_visibility(const float* albedo_occ4, uint32_t n, v3 q, v3 l) {
     float tdx = sx ? 1.0f / fabsf(l.x) : INFINITY;
     float tdy = sy ? 1.0f / fabsf(l.y) : INFINITY;
     float tdz = sz ? 1.0f / fabsf(l.z) : INFINITY;
+    if (tdx == INFINITY) sx = 0;
+    if (tdy == INFINITY) sy = 0;
+    if (tdz == INFINITY) sz = 0;
     float tmx = sx > 0 ? ((float)(vx + 1) - q.x) * tdx : (sx < 0 ? (q.x - (float)vx) * tdx : INFINITY);
     float tmy = sy > 0 ? ((float)(vy + 1) - q.y) * tdy : (sy < 0 ? (q.y - (float)vy) * tdy : INFINITY);
     float tmz = sz > 0 ? ((float)(vz + 1) - q.z) * tdz : (sz < 0 ? (q.z - (float)vz) * tdz : INFINITY);

@@ -37,15 +37,16 @@ def prepare(light, n, g0, E):
         d = _f3(light.direction)
         out["l"] = d / np.sqrt(dot3(d[0], d[1], d[2], d[0], d[1], d[2]))
         return out
-    out["pL"] = (_f3(light.position) - g0) * inv_h
-    rv = F(light.range) * inv_h
-    out["inv_rr"] = F(1.0) / (rv * rv)
-    out["h2"] = hh * hh
-    if t == SPOT:
-        d = _f3(light.direction)
-        out["a"] = -(d / np.sqrt(dot3(d[0], d[1], d[2], d[0], d[1], d[2])))
-        out["cos_outer"] = F(light.cos_outer)
-        out["inv_span"] = F(1.0) / (F(light.cos_inner) - F(light.cos_outer))
+    with np.errstate(all="ignore"):                  # overflowing ranges and one-ulp spans are legal
+        out["pL"] = (_f3(light.position) - g0) * inv_h
+        rv = F(light.range) * inv_h
+        out["inv_rr"] = F(1.0) / (rv * rv)
+        out["h2"] = hh * hh
+        if t == SPOT:
+            d = _f3(light.direction)
+            out["a"] = -(d / np.sqrt(dot3(d[0], d[1], d[2], d[0], d[1], d[2])))
+            out["cos_outer"] = F(light.cos_outer)
+            out["inv_span"] = F(1.0) / (F(light.cos_inner) - F(light.cos_outer))
     return out
 
 
@@ -97,6 +98,9 @@ def walk(occ, q, l, t_lim):
         end[outside] = 1
         s = np.where(l > 0, 1, np.where(l < 0, -1, 0)).astype(np.int64)
         td = np.where(s != 0, F(1.0) / np.abs(l), INF).astype(F)
+        # K2 input rule (vct_spec.h): an axis whose td is not finite does not move (s_a = 0,
+        # tm_a = +inf), so no t is ever NaN
+        s = np.where(td == INF, 0, s)
         vf = v.astype(F)
         tm = np.where(s > 0, ((vf + F(1.0)) - q) * td, np.where(s < 0, (q - vf) * td, INF)).astype(F)
     t_e = np.zeros(R, F)

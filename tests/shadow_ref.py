@@ -7,7 +7,8 @@ binary32 through spec_ref's scalar helpers), and everything per receiver is one 
 numpy operation in the order the spec gives.  The spec's fused operations go through
 :func:`fmaf`, an exact vectorised binary32 fma.
 
-The per-light terms, the skip rule and the hard walk are tests/lights_ref.py's.
+The per-light terms, the skip rule and the hard walk are tests/lights_ref.py's (the walk under
+the K2 input rule of vct_spec.h: an axis whose td is not finite does not move).
 """
 from __future__ import annotations
 

@@ -291,6 +291,9 @@ def inject(n, ao, nm, light, color=(1.0, 1.0, 1.0)):
             if all(0 <= c < n for c in v):
                 st = [1 if c > 0 else (-1 if c < 0 else 0) for c in l]
                 td = [f32(1.0 / abs(l[i])) if st[i] else inf for i in range(3)]
+                # K2 input rule (vct_spec.h): an axis whose td is not finite does not move
+                # (s_a = 0, tm_a = +inf), so no t is ever NaN
+                st = [0 if td[i] == inf else st[i] for i in range(3)]
                 tm = [f32(f32(float(v[i] + 1) - q[i]) * td[i]) if st[i] > 0 else
                       (f32(f32(q[i] - float(v[i])) * td[i]) if st[i] < 0 else inf) for i in range(3)]
                 while True:

@@ -584,9 +584,13 @@ vct_status vct_set_textures(vct_ctx* c, const vct_texture* tex, uint32_t n) {
 vct_status vct_inject_directional(vct_ctx* c, const float dir[3], const float color[3]) {
     if (!c || !dir || !color) return VCT_EINVAL;
     if (!c->grid.voxelized) return fail(c, VCT_ESTATE, "inject before voxelize");
+    // K2 input rule, direction: len in float32 finite and > 0 (a squared length that underflows
+    // to 0 or overflows to +inf is refused); the colour by check_color (vct_internal.h), the light
+    // list's check; an error leaves level 0 as it was
     float lx = dir[0], ly = dir[1], lz = dir[2];
     const float len = sqrtf((lx * lx + ly * ly) + lz * lz);
     if (!(len > 0.0f) || !std::isfinite(len)) return fail(c, VCT_EINVAL, "zero or non-finite light direction");
+    if (const char* bad = check_color(color)) return fail(c, VCT_EINVAL, std::string("inject: ") + bad);
     lx = lx / len; ly = ly / len; lz = lz / len;
     vct_status st = use_device(c);
     if (st != VCT_OK) return st;
@@ -916,9 +920,11 @@ vct_status vct_composite_device(vct_ctx* c, const float* pos4, const float* nrm4
                           (const void*)spec4, (const void*)out_linear4})
         if (((uintptr_t)p & 15u) != 0) return fail(c, VCT_EINVAL, "composite: float4 buffers must be 16-byte aligned");
     if (((uintptr_t)out_rgba8 & 3u) != 0) return fail(c, VCT_EINVAL, "composite: rgba8 buffer must be 4-byte aligned");
-    float l[3] = {dir_to_light[0], dir_to_light[1], dir_to_light[2]};   // normalized as vct_inject_directional
+    // K2 input rule: direction and colour as vct_inject_directional checks and normalizes them
+    float l[3] = {dir_to_light[0], dir_to_light[1], dir_to_light[2]};
     const float len = sqrtf((l[0] * l[0] + l[1] * l[1]) + l[2] * l[2]);
     if (!(len > 0.0f) || !std::isfinite(len)) return fail(c, VCT_EINVAL, "zero or non-finite light direction");
+    if (const char* bad = check_color(color)) return fail(c, VCT_EINVAL, std::string("composite: ") + bad);
     l[0] = l[0] / len; l[1] = l[1] / len; l[2] = l[2] / len;
     vct_status st = use_device(c);
     if (st != VCT_OK) return st;

@@ -84,6 +84,8 @@ __device__ __forceinline__ bool occ_at(const unsigned long long* __restrict__ bi
 
 // A.3 shadow walk (Amanatides-Woo) from q (voxel units) toward l over the
 // level-0 occupancy bits: 1 = leaves the grid unblocked, 0 = hits a voxel.
+// K2 input rule (vct_spec.h): an axis whose td is not finite -- l_a == 0, or |l_a| <= 2^-128,
+// whose reciprocal overflows -- does not move (s_a = 0, tm_a = +inf), so no t is ever NaN.
 __device__ __forceinline__ float dda_visibility(const unsigned long long* __restrict__ bits, int N, float qx, float qy,
                                 float qz, float lx, float ly, float lz) {
     int vx = (int)floorf(qx), vy = (int)floorf(qy), vz = (int)floorf(qz);
@@ -95,6 +97,9 @@ __device__ __forceinline__ float dda_visibility(const unsigned long long* __rest
     float tdx = sx ? 1.0f / fabsf(lx) : inf;
     float tdy = sy ? 1.0f / fabsf(ly) : inf;
     float tdz = sz ? 1.0f / fabsf(lz) : inf;
+    if (tdx == inf) sx = 0;
+    if (tdy == inf) sy = 0;
+    if (tdz == inf) sz = 0;
     float tmx = sx > 0 ? ((float)(vx + 1) - qx) * tdx : (sx < 0 ? (qx - (float)vx) * tdx : inf);
     float tmy = sy > 0 ? ((float)(vy + 1) - qy) * tdy : (sy < 0 ? (qy - (float)vy) * tdy : inf);
     float tmz = sz > 0 ? ((float)(vz + 1) - qz) * tdz : (sz < 0 ? (qz - (float)vz) * tdz : inf);

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cmath>
 #include <string>
 #include <vector>
 #include "../../include/vct.h"
@@ -273,6 +274,19 @@ struct vct_ctx {
 };
 
 namespace vct {
+
+// K2 input rule, colour (vct_spec.h): finite, not negative (-0.0f by its sign bit) and
+// <= VCT_COLOR_LIMIT, which keeps level 0 finite; nullptr, or what is wrong.  The one check of
+// vct_inject_directional, vct_composite_device (vct_capi.cpp) and every light of a list
+// (prepare_light, vct_light_terms.h).
+inline const char* check_color(const float* color) {
+    for (int k = 0; k < 3; ++k) {
+        if (!std::isfinite(color[k])) return "non-finite colour";
+        if (!(color[k] >= 0.0f) || std::signbit(color[k])) return "negative colour";
+        if (color[k] > VCT_COLOR_LIMIT) return "colour above VCT_COLOR_LIMIT";
+    }
+    return nullptr;
+}
 
 // K1
 // d_map (device, n_mat entries, may be NULL): diffuse map of each material in c->tex

@@ -56,18 +56,22 @@ __device__ __forceinline__ bool light_terms(const DLight& L, float h2, float qx,
 }
 
 // The spec's V, plainly: dda_visibility (vct_device.h) with the entry parameter t_e of the
-// current cell and the end t_e >= t_lim.
+// current cell and the end t_e >= t_lim.  K2 input rule: an axis whose td is not finite does
+// not move (s_a = 0, tm_a = +inf), so no t is ever NaN.
 __device__ __forceinline__ float dda_lim(const unsigned long long* __restrict__ bits, int N, float qx, float qy,
                                          float qz, float lx, float ly, float lz, float t_lim) {
     int vx = (int)floorf(qx), vy = (int)floorf(qy), vz = (int)floorf(qz);
     if (vx < 0 || vy < 0 || vz < 0 || vx >= N || vy >= N || vz >= N) return 1.0f;
-    const int sx = lx > 0.0f ? 1 : (lx < 0.0f ? -1 : 0);
-    const int sy = ly > 0.0f ? 1 : (ly < 0.0f ? -1 : 0);
-    const int sz = lz > 0.0f ? 1 : (lz < 0.0f ? -1 : 0);
+    int sx = lx > 0.0f ? 1 : (lx < 0.0f ? -1 : 0);
+    int sy = ly > 0.0f ? 1 : (ly < 0.0f ? -1 : 0);
+    int sz = lz > 0.0f ? 1 : (lz < 0.0f ? -1 : 0);
     const float inf = __builtin_inff();
     const float tdx = sx ? 1.0f / fabsf(lx) : inf;
     const float tdy = sy ? 1.0f / fabsf(ly) : inf;
     const float tdz = sz ? 1.0f / fabsf(lz) : inf;
+    if (tdx == inf) sx = 0;
+    if (tdy == inf) sy = 0;
+    if (tdz == inf) sz = 0;
     float tmx = sx > 0 ? ((float)(vx + 1) - qx) * tdx : (sx < 0 ? (qx - (float)vx) * tdx : inf);
     float tmy = sy > 0 ? ((float)(vy + 1) - qy) * tdy : (sy < 0 ? (qy - (float)vy) * tdy : inf);
     float tmz = sz > 0 ? ((float)(vz + 1) - qz) * tdz : (sz < 0 ? (qz - (float)vz) * tdz : inf);
@@ -102,14 +106,15 @@ const char* prepare_light(const Grid& g, const vct_light& in, DLight& out) {
     if (!finite3(in.position) || !finite3(in.direction) || !finite3(in.color) || !std::isfinite(in.range) ||
         !std::isfinite(in.cos_inner) || !std::isfinite(in.cos_outer))
         return "non-finite field";
-    for (int k = 0; k < 3; ++k)
-        if (!(in.color[k] >= 0.0f) || std::signbit(in.color[k])) return "negative colour";
+    if (const char* bad = check_color(in.color)) return bad;   // K2 input rule, colour (vct_internal.h)
     out = DLight{};
     out.type = in.type;
     out.cr = in.color[0]; out.cg = in.color[1]; out.cb = in.color[2];
     float ux = 0.0f, uy = 0.0f, uz = 0.0f;
     if (in.type != VCT_LIGHT_POINT) {
         const float dx = in.direction[0], dy = in.direction[1], dz = in.direction[2];
+        // K2 input rule, direction: len in float32 finite and > 0 (a squared length that
+        // underflows to 0 or overflows to +inf is refused)
         const float len = sqrtf((dx * dx + dy * dy) + dz * dz);
         if (!(len > 0.0f) || !std::isfinite(len)) return "zero or non-finite light direction";
         ux = dx / len; uy = dy / len; uz = dz / len;

@@ -75,7 +75,9 @@ __device__ __forceinline__ float dda_coarse_lim(__amdgpu_buffer_rsrc_t bits, con
             const unsigned long long row = cb[((uy >> cs) | ((uz >> cs) << lgcn)) & (uint32_t)(kCoarseRows - 1)];
             co |= ((uint32_t)(row >> ((ux >> cs) & 63u)) & (uint32_t)valid) << b;
             if (COUNT) vm |= (uint32_t)valid << b;
-            // the spec's choice (x if tmx <= tmy, tmz; else y if tmy <= tmz; else z) from the minimum
+            // the spec's choice (x if tmx <= tmy, tmz; else y if tmy <= tmz; else z) from the
+            // minimum, as dda_coarse has it: an axis whose td is +inf (K2 input rule) has a tm of
+            // +inf or NaN and is never the minimum, so tmin is the chosen axis's t, never NaN
             const float tmin = fminf(fminf(tmx, tmy), tmz);
             const bool bx = tmx == tmin;
             const bool by = !bx && tmy == tmin;

@@ -640,7 +640,9 @@ __device__ __forceinline__ float dda_coarse(__amdgpu_buffer_rsrc_t bits, const u
             const unsigned long long row = cb[((uy >> cs) | ((uz >> cs) << lgcn)) & (uint32_t)(kCoarseRows - 1)];
             co |= ((uint32_t)(row >> ((ux >> cs) & 63u)) & (uint32_t)in) << b;
             // the spec's choice (x if tmx <= tmy, tmz; else y if tmy <= tmz; else z) from the
-            // minimum: no t is NaN
+            // minimum.  K2 input rule: an axis whose td is +inf never moves.  Its tm is +inf, or
+            // NaN (0 * inf at an integer q); fminf drops a NaN and == is false for one, and the
+            // other axes' t stay finite, so such an axis is never the minimum
             const float tmin = fminf(fminf(tmx, tmy), tmz);
             const bool bx = tmx == tmin;
             const bool by = !bx && tmy == tmin;
