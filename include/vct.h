@@ -423,5 +423,6 @@ vct_status vct_dump_info(const char* stem, vct_config* cfg, uint32_t* what);
 #include "vct_lights.h"
 /* ---- cone-traced soft shadows (additive; HIP library only) ------------------------ */
 #include "vct_shadow.h"
+#include "vct_emission.h"   /* emissive surfaces (additive; HIP library only) */
 
 #endif /* VCT_H */

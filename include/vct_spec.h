@@ -294,4 +294,50 @@
  *  (final = (direct + A * D) + S).  With every tan_half 0 it is vct_composite_lights_device
  *  bit for bit. */
 
+/* ---- emissive surfaces (vct_voxelize_emission* / vct_inject_emission /
+ *      vct_composite_emissive_device, include/vct_emission.h) ------------------------------
+ * The emission grid reuses VCT_FIXED_ONE and VCT_KD_LIMIT and adds no literal of its own.
+ *  Ke_c(t) = component c of material_ke4[material of t] (tri_material NULL: material 0).
+ *  count(v) = K1's hit count of voxel v in the CURRENT voxelization (the grid the emission
+ *  grid is built on).
+ *      fix_c(t) = (int64)roundf(Ke_c(t) * VCT_FIXED_ONE)
+ *      S_c(v)   = sum of fix_c(t) over the triangles t of THIS call whose SAT covers v
+ *      E_c(v)   = (float)((double)S_c(v) / ((double)count(v) * VCT_FIXED_ONE_D))   for count(v) > 0
+ *      v is emissive iff count(v) > 0 and some S_c(v) != 0.
+ *    "covers" is K1's test, unchanged: the same q = (p - g0) * inv_h per vertex, the candidate
+ *    range of the "K1 input rule", the same 13-axis test, touching counts.  The sums are
+ *    integers, so they do not depend on the order of the triangles.
+ *  A hit in a voxel with count(v) == 0 (emitter geometry that is not part of the voxelized
+ *    mesh) is dropped: the emissive voxels are a subset of the occupied ones.  When the
+ *    emitters are the voxelized mesh, or a subset of its triangles, E(v) is the average of Ke
+ *    over ALL triangles touching v, as the albedo is the average of Kd.
+ *  A triangle whose three fix_c are 0 adds nothing and has no candidates.
+ *  Input rule.  Vertices: the K1 input rule (any finite vertex is legal; a triangle with a
+ *    non-finite component of q is skipped, and is not an error).  Ke.r, .g, .b of every material
+ *    a triangle uses must be finite, have a clear sign bit (-0.0f is refused, as the K2 input
+ *    rule refuses it for a colour) and be < VCT_KD_LIMIT; otherwise, and for an index out of
+ *    range or a NULL material_ke4, the call is an error (VCT_EINVAL) and the emission grid is
+ *    empty afterwards.  Ke.a is not read.  With Ke >= 0, fix < 2^31 and a 32-bit count, S
+ *    cannot overflow 64 bits, and E_c <= max Ke_c < 2^15.
+ *  Lifetime: every vct_voxelize* and vct_load_grid empties the emission grid; vct_save_grid
+ *    does not store it.
+ *  vct_inject_emission(scale): at every emissive voxel, per colour channel,
+ *      L_c = L_c + (scale * E_c)                  (one multiply, then one add; no fma)
+ *    on the level-0 texel of the voxel; alpha and every other voxel are untouched.
+ *    scale must be finite, have a clear sign bit and be <= VCT_EMISSION_SCALE_LIMIT.  The
+ *    limit keeps level 0 finite: E < VCT_KD_LIMIT = 2^15, so scale * E < 2^111 * 2^15 = 2^126;
+ *    K2's sum is below 2^127 ("K2 input rule", colour); their sum is below
+ *    2^127 + 2^126 = 1.5 * 2^127 < FLT_MAX = (2 - 2^-23) * 2^127.
+ *      VCT_EMISSION_SCALE_LIMIT = 2^126 / VCT_KD_LIMIT = 2^111.
+ *  vct_composite_emissive_device: the receiver, the lights and V are those of "shadow cones"
+ *    (vis given) or "local lights" (vis NULL: the walk); then
+ *      p_c = (P_c - g0_c) * inv_h                 (the pixel's position, no normal offset)
+ *      Em  = E(v) with v_c = (int)floorf(p_c) if 0 <= p_c < (float)n holds in float32 for all
+ *            three axes (a NaN fails it) and v is emissive; else +0 in every channel
+ *      final_c = ((direct_c + A_c * D_c) + S_c) + scale * Em_c      (the product, then one add)
+ *    Background pixels get the clear colour as in every composite.  With an empty emission
+ *    grid or scale = +0 the term is left out, so the result is the other composites' bit for
+ *    bit. */
+#define VCT_EMISSION_SCALE_LIMIT 2.59614843e33f  /* 2^111 exactly */
+
 #endif /* VCT_SPEC_H */

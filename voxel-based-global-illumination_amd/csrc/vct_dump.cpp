@@ -141,7 +141,7 @@ struct InvalidateOnFail {
     ~InvalidateOnFail() {
         if (!armed) return;
         Grid& g = c->grid;
-        g.voxelized = g.injected = g.mipped = g.bounced = false;
+        g.voxelized = g.injected = g.mipped = g.bounced = g.emitted = false;
         g.k2_coarse_ok = g.k3_sparse_ok = g.zm_valid = false;
         ++c->grid_epoch;
     }
@@ -161,6 +161,7 @@ vct_status vct_load_grid(vct_ctx* c, const char* stem) {
     Grid& g = c->grid;
     const size_t nv = (size_t)g.n * g.n * g.n;
     VCT_DHIP(hipSetDevice(c->device), "hipSetDevice");
+    c->em.built = false;   // a dump holds no emission grid: every load empties it (vct_emission.h)
     if (h.what & VCT_DUMP_VOXELS) {
         const size_t occ = (size_t)h.occupied;
         std::vector<uint32_t> idx(occ), counts(occ);
@@ -186,7 +187,7 @@ vct_status vct_load_grid(vct_ctx* c, const char* stem) {
         }
         // what a voxelization invalidates (voxelize_dev), then K1's state written back
         guard.armed = true;
-        g.voxelized = g.injected = g.mipped = g.bounced = false;
+        g.voxelized = g.injected = g.mipped = g.bounced = g.emitted = false;
         g.k2_coarse_ok = g.k3_sparse_ok = g.zm_valid = false;
         g.k3_live_bz = 0;
         ++c->grid_epoch;

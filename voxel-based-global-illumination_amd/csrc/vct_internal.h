@@ -77,6 +77,29 @@ struct Grid {
     bool l0_dense = false;   // level 0 was replaced densely (upload / device copy): K2 must clear it whole
     bool l0_on_peers = false;   // multi-device: the other devices hold this level 0 (vct_build_mips copies it)
     bool bounced = false;       // vct_inject_bounces has added to this level 0 (cleared with every new level 0)
+    bool emitted = false;       // vct_inject_emission has added to this level 0 (cleared where bounced is)
+};
+
+// Emissive surfaces (vct_emission.hip; vct_spec.h "emissive surfaces").  The emission grid
+// E of the current voxelization, sparse: one bit per voxel, the number of emissive voxels
+// before each 64-voxel word, and the emissive voxels' index and E in bitmask order, so
+//     rank(v) = prefix[v >> 6] + popc(bits[v >> 6] & ((1ull << (v & 63)) - 1))
+// finds a voxel's entry in O(1).  The integer sums are accumulated per OCCUPIED voxel
+// (rank among K1's occupancy bits: a hit outside them is dropped), so nothing here is sized
+// by n^3 but the bit and prefix words (3 n^3 / 16 bytes).  Allocated by the first
+// vct_voxelize_emission*, grown when a voxelization occupies more voxels.
+struct Emission {
+    unsigned long long* bits = nullptr;   // [n^3 / 64] emissive voxels
+    uint32_t* prefix = nullptr;           // [n^3 / 64] emissive voxels before word w
+    long long* sums = nullptr;            // [cap][3] S rgb per occupied voxel (occupancy rank)
+    uint32_t* vox = nullptr;              // [cap] linear-Z voxel of entry i (entries < *count)
+    float4* E = nullptr;                  // [cap] (E rgb, 1) of entry i
+    uint32_t* count = nullptr;            // [1] emissive voxels (device)
+    size_t cap = 0;                       // entries sums / vox / E hold
+    bool built = false;                   // E belongs to the voxelization `epoch` (else: empty)
+    bool maybe = false;                   // built, and some triangle had candidates (the count may be > 0)
+    uint32_t epoch = 0;                   // vct_ctx::grid_epoch of the build
+    int64_t n_host = -1;                  // the count once read back (vct_emission_voxels), -1 unknown
 };
 
 struct Mesh {
@@ -232,7 +255,8 @@ struct vct_ctx {
     vct::Scratch scratch[12];    // reusable scratch (0 trace host staging, 1 voxelize temps,
                                   // 2-3 G-buffer bins, 4 K2 work list, 7 K1 candidate bucket table,
                                   // 8 multi-device tiles / gather, 9 multi-device step counters,
-                                  // 10 shadow-cone step tables)
+                                  // 10 shadow-cone step tables, 11 occupancy ranks of the emission build,
+                                  // which also reuses 1 and 7 as K1 does)
     float shadow_tau[VCT_MAX_LIGHTS] = {};   // the apertures whose step tables scratch 10 holds, slot by slot
     uint32_t shadow_taus = 0;                // (vct_shadow.hip; 0: none built yet)
     // The tables are shared by every vct_shadow_cones_device call whatever stream the caller
@@ -246,6 +270,7 @@ struct vct_ctx {
     vct::StreamScratch k4s[vct::kStreamSets];   // K4 hand-over + reorder scratch per stream (k4_scratch)
     vct::K4Tuner k4tune;                // timed-form choice of the default cone trace
     vct::Bounce bounce;                 // source list of vct_inject_bounces
+    vct::Emission em;                   // emission grid of vct_voxelize_emission*
     uint32_t grid_epoch = 0;            // bumped by every voxelization (a new scene for the tuner)
     vct::StepRow* step_tab = nullptr;   // [kMaxStepRows] diffuse-cone step table (device)
     unsigned* spec_keys = nullptr;      // [2 * kSpecSlots]: specular table keys (~0u free), then states
@@ -328,6 +353,12 @@ hipError_t launch_bounce_save(vct_ctx* c);
 hipError_t launch_bounce_gather(vct_ctx* c);
 hipError_t launch_bounce_accumulate(vct_ctx* c);
 void bounce_free(vct_ctx* c);
+// emissive surfaces (vct_emission.hip): the context's emission grid is the one built for the
+// current voxelization, and may hold an emissive voxel; release with the context
+inline bool emission_live(const vct_ctx* c) {
+    return c->em.built && c->em.epoch == c->grid_epoch && c->em.maybe && c->em.n_host != 0;
+}
+void emission_free(vct_ctx* c);
 // ray reordering (variant 0x8000, vct_reorder.hip): *perm = the frame's pixels sorted by the
 // Morton code of their cone origin's voxel, background last (device, w * h entries)
 // (perm_spec, nullable: a second order for the specular part, by cell and cone aperture)

@@ -21,6 +21,7 @@
 #include <cstring>
 
 #include "vct_internal.h"
+#include "vct_voxel_sat.h"   // the candidate record and range, the scan, the SAT, the bucket table
 
 #ifdef VCT_DEBUG_WAVES
 // per-wave (start, end, HW_ID | XCC_ID << 32) of the last k2_walk launch (timeline build,
@@ -40,12 +41,6 @@ extern "C" int vct_debug_k2_waves_clear() {
 namespace vct {
 namespace {
 
-struct TriGeom {      // 64 B
-    float q[9];       // voxel-unit vertex positions
-    int lo[3];        // first candidate voxel per axis
-    uint32_t ext[3];  // candidate extent per axis (0 = no candidates)
-    uint32_t pad;
-};
 struct TriFix {       // 64 B
     long long fix[6]; // albedo rgb, face normal xyz in 16.16 fixed point
     long long tex;    // diffuse map of the triangle's material (-1: albedo = Kd, fix[0..2])
@@ -56,18 +51,6 @@ struct TriUV {        // 48 B, textured triangles only
     float kd[3];      // material Kd (albedo = Kd x T(uv) per hit)
     uint32_t pad[3];
 };
-
-__device__ __forceinline__ float fmin3(float a, float b, float c) { return fminf(fminf(a, b), c); }
-__device__ __forceinline__ float fmax3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
-
-// vct_spec.h "K1 input rule": both ends clamped to [-1, n + 1] before the conversion
-__device__ __forceinline__ void cand_range(float mn, float mx, int n, int& lo, int& hi) {
-    const float top = (float)n + 1.0f;
-    int l = (int)ceilf(fminf(fmaxf(mn, -1.0f), top)) - 1;
-    int h = (int)floorf(fmaxf(fminf(mx, top), -1.0f));
-    lo = l < 0 ? 0 : l;
-    hi = h > n - 1 ? n - 1 : h;
-}
 
 __global__ void __launch_bounds__(256) k1_tri_setup(
     const char* __restrict__ verts, uint32_t stride, uint32_t n_verts,
@@ -187,129 +170,6 @@ __global__ void __launch_bounds__(256) k1_tri_setup(
     mesh_tri[4 * t + 1] = make_float4(e1[0], e1[1], e1[2], 0.0f);
     mesh_tri[4 * t + 2] = make_float4(e2[0], e2[1], e2[2], 0.0f);
     mesh_tri[4 * t + 3] = make_float4(alb.x, alb.y, alb.z, __int_as_float(tex));
-}
-
-// ---- exclusive scan of per-triangle candidate counts (u64) ----------------
-constexpr int kScanBlock = 256, kScanItems = 4, kScanTile = kScanBlock * kScanItems;
-
-__device__ __forceinline__ unsigned long long block_excl_scan(unsigned long long v,
-                                                             unsigned long long* sh,
-                                                             unsigned long long& total) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    unsigned long long x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        unsigned long long y = __shfl_up(x, off, 64);
-        if (lane >= off) x += y;
-    }
-    if (lane == 63) sh[wid] = x;
-    __syncthreads();
-    unsigned long long base = 0;
-    for (int w = 0; w < wid; ++w) base += sh[w];
-    total = sh[0] + sh[1] + sh[2] + sh[3];
-    __syncthreads();
-    return base + x - v;
-}
-
-__global__ void __launch_bounds__(kScanBlock) k_scan_tiles(const unsigned long long* __restrict__ in,
-                                                           unsigned long long* __restrict__ out,
-                                                           unsigned long long* __restrict__ tile_sums,
-                                                           uint32_t count) {
-    __shared__ unsigned long long sh[4];
-    const size_t base = (size_t)blockIdx.x * kScanTile + (size_t)threadIdx.x * kScanItems;
-    unsigned long long v[kScanItems], s = 0;
-#pragma unroll
-    for (int i = 0; i < kScanItems; ++i) {
-        v[i] = base + i < count ? in[base + i] : 0ull;
-        s += v[i];
-    }
-    unsigned long long total;
-    unsigned long long ex = block_excl_scan(s, sh, total);
-#pragma unroll
-    for (int i = 0; i < kScanItems; ++i) {
-        if (base + i < count) out[base + i] = ex;
-        ex += v[i];
-    }
-    if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
-}
-
-// single-block carry scan over the tile sums (n_tiles small: n_tri / 1024)
-__global__ void __launch_bounds__(kScanBlock) k_scan_carry(unsigned long long* __restrict__ tile_sums,
-                                                           uint32_t n_tiles,
-                                                           unsigned long long* __restrict__ total_out) {
-    __shared__ unsigned long long sh[4];
-    unsigned long long carry = 0;
-    for (uint32_t b = 0; b < n_tiles; b += kScanBlock) {
-        uint32_t i = b + threadIdx.x;
-        unsigned long long v = i < n_tiles ? tile_sums[i] : 0ull, tot;
-        unsigned long long ex = block_excl_scan(v, sh, tot);
-        if (i < n_tiles) tile_sums[i] = carry + ex;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) *total_out = carry;
-}
-
-__global__ void __launch_bounds__(kScanBlock) k_scan_add(unsigned long long* __restrict__ out,
-                                                         const unsigned long long* __restrict__ tile_sums,
-                                                         uint32_t count) {
-    const size_t base = (size_t)blockIdx.x * kScanTile;
-    const unsigned long long add = tile_sums[blockIdx.x];
-    for (int i = threadIdx.x; i < kScanTile; i += kScanBlock)
-        if (base + i < count) out[base + i] += add;
-}
-
-// ---- exact 13-axis triangle/voxel SAT (same rule as oracle/vct_oracle.c) --
-__device__ __forceinline__ bool tri_box_overlap(const float* __restrict__ q, float cx, float cy, float cz) {
-    float a0x = q[0] - cx, a0y = q[1] - cy, a0z = q[2] - cz;
-    float a1x = q[3] - cx, a1y = q[4] - cy, a1z = q[5] - cz;
-    float a2x = q[6] - cx, a2y = q[7] - cy, a2z = q[8] - cz;
-    if (fmin3(a0x, a1x, a2x) > 0.5f || fmax3(a0x, a1x, a2x) < -0.5f) return false;
-    if (fmin3(a0y, a1y, a2y) > 0.5f || fmax3(a0y, a1y, a2y) < -0.5f) return false;
-    if (fmin3(a0z, a1z, a2z) > 0.5f || fmax3(a0z, a1z, a2z) < -0.5f) return false;
-    float e[3][3] = {{a1x - a0x, a1y - a0y, a1z - a0z},
-                     {a2x - a1x, a2y - a1y, a2z - a1z},
-                     {a0x - a2x, a0y - a2y, a0z - a2z}};
-    {
-        float nx = e[0][1] * e[1][2] - e[0][2] * e[1][1];
-        float ny = e[0][2] * e[1][0] - e[0][0] * e[1][2];
-        float nz = e[0][0] * e[1][1] - e[0][1] * e[1][0];
-        float vminx, vmaxx, vminy, vmaxy, vminz, vmaxz;
-        if (nx > 0.0f) { vminx = -0.5f - a0x; vmaxx = 0.5f - a0x; } else { vminx = 0.5f - a0x; vmaxx = -0.5f - a0x; }
-        if (ny > 0.0f) { vminy = -0.5f - a0y; vmaxy = 0.5f - a0y; } else { vminy = 0.5f - a0y; vmaxy = -0.5f - a0y; }
-        if (nz > 0.0f) { vminz = -0.5f - a0z; vmaxz = 0.5f - a0z; } else { vminz = 0.5f - a0z; vmaxz = -0.5f - a0z; }
-        if (dot3(nx, ny, nz, vminx, vminy, vminz) > 0.0f) return false;
-        if (!(dot3(nx, ny, nz, vmaxx, vmaxy, vmaxz) >= 0.0f)) return false;
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float ex = e[i][0], ey = e[i][1], ez = e[i][2];
-        const float ax[3][3] = {{0.0f, -ez, ey}, {ez, 0.0f, -ex}, {-ey, ex, 0.0f}};
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const float ux = ax[j][0], uy = ax[j][1], uz = ax[j][2];
-            float p0 = dot3(ux, uy, uz, a0x, a0y, a0z);
-            float p1 = dot3(ux, uy, uz, a1x, a1y, a1z);
-            float p2 = dot3(ux, uy, uz, a2x, a2y, a2z);
-            float rad = 0.5f * ((fabsf(ux) + fabsf(uy)) + fabsf(uz));
-            if (fmin3(p0, p1, p2) > rad || fmax3(p0, p1, p2) < -rad) return false;
-        }
-    }
-    return true;
-}
-
-constexpr int kCandPerThread = 8;
-constexpr int kCandBucket = 512;                 // candidates per bucket of the triangle-lookup table
-
-// bucket b -> the triangle holding candidate b * kCandBucket (triangles whose
-// candidate range crosses a bucket start write it; a giant triangle writes many)
-__global__ void __launch_bounds__(256) k1_bucket_starts(const unsigned long long* __restrict__ offs, uint32_t n_tri,
-                                                        const unsigned long long* __restrict__ total_p,
-                                                        uint32_t* __restrict__ starts) {
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_tri) return;
-    const unsigned long long lo = offs[t], hi = t + 1 < n_tri ? offs[t + 1] : *total_p;
-    if (hi <= lo) return;                        // no candidates
-    for (unsigned long long b = (lo + kCandBucket - 1) / kCandBucket; b * kCandBucket < hi; ++b) starts[b] = t;
 }
 
 // one lane = kCandPerThread consecutive (triangle, voxel) candidates.  PACKED: a hit adds
@@ -478,26 +338,6 @@ __device__ __forceinline__ void resolve_voxel(const long long* __restrict__ accu
 //              (same cells, same float sequence, same result).
 // Level 0 is zeroed first; every voxel's value depends on that voxel alone, so
 // the list order (waves append in any order) does not change the output.
-// exclusive prefix sum of one value per thread over a 256-thread block, and the
-// block total (4 waves: shuffles within the wave, wave totals through LDS)
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t& total) {
-    __shared__ uint32_t wt[4];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t t = __shfl_up(incl, off, 64);
-        if (lane >= (uint32_t)off) incl += t;
-    }
-    if (lane == 63) wt[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0;
-    for (uint32_t w = 0; w < wave; ++w) before += wt[w];
-    total = wt[0] + wt[1] + wt[2] + wt[3];
-    __syncthreads();
-    return before + incl - v;
-}
-
 __device__ __forceinline__ uint32_t lanes_below(unsigned long long m) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }

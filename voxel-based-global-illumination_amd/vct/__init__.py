@@ -489,6 +489,81 @@ class Context:
             self._dev(out_linear4, "out_linear4", _F32, n),
             self._dev(out_rgba8, "out_rgba8", _I32, width * height)), "composite_shadowed")
 
+    # -- emissive surfaces (include/vct_emission.h) -------------------------
+    def voxelize_emission(self, verts: np.ndarray, idx: np.ndarray, tri_material: np.ndarray | None,
+                          ke4: np.ndarray):
+        """vct_voxelize_emission: the emission grid of the current voxelization from emitter
+        triangles (the voxelized mesh or a subset of it) and ke4 [materials, 4], Ke per material."""
+        fn = _lib.bind_emission_extension(self.lib, "vct_voxelize_emission")
+        verts = np.ascontiguousarray(verts, dtype=np.float32)
+        assert verts.ndim == 2 and verts.shape[1] >= 3
+        idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+        mat = None if tri_material is None else np.ascontiguousarray(tri_material, dtype=np.uint32).reshape(-1)
+        ke = None if ke4 is None else np.ascontiguousarray(ke4, dtype=np.float32)
+        if idx.size % 3:
+            raise VctError(_EINVAL, f"voxelize_emission: {idx.size} indices, not a multiple of 3")
+        if mat is not None and mat.size != idx.size // 3:
+            raise VctError(_EINVAL, f"voxelize_emission: tri_material has {mat.size} entries for "
+                                    f"{idx.size // 3} triangles")
+        if ke is not None and (ke.ndim != 2 or ke.shape[1] != 4):
+            raise VctError(_EINVAL, f"voxelize_emission: ke4 must be [materials, 4], got {ke.shape}")
+        self._check(fn(self.h, _fptr(verts), verts.shape[1] * 4, verts.shape[0], _fptr(idx), idx.size,
+                       _fptr(mat) if mat is not None else None, _fptr(ke) if ke is not None else None,
+                       0 if ke is None else ke.shape[0]), "voxelize_emission")
+
+    def voxelize_emission_device(self, verts, idx, tri_material, ke4):
+        """vct_voxelize_emission_device on torch tensors: verts [V, F >= 3] float32, idx [3T]
+        int32 / uint32, tri_material [T] int32 or None, ke4 [M, 4] float32."""
+        fn = _lib.bind_emission_extension(self.lib, "vct_voxelize_emission_device")
+        if verts.dim() != 2 or verts.shape[1] < 3:
+            raise VctError(_EINVAL, f"voxelize_emission_device: verts must be [V, F >= 3], got {tuple(verts.shape)}")
+        if str(idx.dtype) in _I64:
+            raise VctError(_EINVAL, "voxelize_emission_device: idx must be int32 / uint32, not 64-bit")
+        n_idx = idx.numel()
+        if n_idx % 3:
+            raise VctError(_EINVAL, f"voxelize_emission_device: {n_idx} indices, not a multiple of 3")
+        if ke4 is not None and not isinstance(ke4, int) and (ke4.dim() != 2 or ke4.shape[1] != 4):
+            raise VctError(_EINVAL, f"voxelize_emission_device: ke4 must be [materials, 4], got {tuple(ke4.shape)}")
+        nm = 0 if ke4 is None or isinstance(ke4, int) else ke4.shape[0]
+        self._check(fn(self.h, self._dev(verts, "verts"), verts.shape[1] * 4, verts.shape[0],
+                       self._dev(idx, "idx", _I32), n_idx, self._dev(tri_material, "tri_material", _I32, n_idx // 3),
+                       self._dev(ke4, "ke4"), nm), "voxelize_emission_device")
+
+    def emission_voxels(self) -> int:
+        """vct_emission_voxels: emissive voxels of the emission grid (0 for an empty one)."""
+        fn = _lib.bind_emission_extension(self.lib, "vct_emission_voxels")
+        n = C.c_uint32()
+        self._check(fn(self.h, C.byref(n)), "emission_voxels")
+        return int(n.value)
+
+    def download_emission(self) -> np.ndarray:
+        """vct_download_emission: [n, n, n, 4] float32 (z, y, x): (E.rgb, 1) at the emissive
+        voxels, +0 elsewhere."""
+        fn = _lib.bind_emission_extension(self.lib, "vct_download_emission")
+        out = np.empty((self.n, self.n, self.n, 4), np.float32)
+        self._check(fn(self.h, _fptr(out)), "download_emission")
+        return out
+
+    def inject_emission(self, scale: float = 1.0):
+        """vct_inject_emission: level 0 += scale * E (after an inject or upload, before
+        build_mips and inject_bounces).  Once per level 0: VctError(ESTATE) on a second call."""
+        fn = _lib.bind_emission_extension(self.lib, "vct_inject_emission")
+        self._check(fn(self.h, float(scale)), "inject_emission")
+
+    def composite_emissive_device(self, pos4, nrm4, alb4, diffuse4, spec4, width, height, lights, vis=None,
+                                  scale: float = 1.0, out_linear4=None, out_rgba8=None):
+        """composite_shadowed_device plus scale * E of the pixel's voxel; vis=None: every light
+        takes the hard voxel walk (composite_lights_device's direct term)."""
+        fn = _lib.bind_emission_extension(self.lib, "vct_composite_emissive_device")
+        arr, nl = _light_array(lights)
+        n = 4 * width * height
+        self._check(fn(
+            self.h, *self._gbuf_ptrs(width, height, pos4, nrm4, alb4), self._dev(diffuse4, "diffuse4", _F32, n),
+            self._dev(spec4, "spec4", _F32, n), width, height, arr, nl,
+            self._dev(vis, "vis", _F32, nl * width * height), float(scale),
+            self._dev(out_linear4, "out_linear4", _F32, n),
+            self._dev(out_rgba8, "out_rgba8", _I32, width * height)), "composite_emissive")
+
     # -- grid access ------------------------------------------------------
     def download_level(self, level: int, face: int = 0) -> np.ndarray:
         nl, _ = self.level_dims(level)

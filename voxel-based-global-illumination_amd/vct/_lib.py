@@ -42,6 +42,11 @@ VCT_MAX_LIGHTS = 64
 # include/vct_shadow.h: cone-traced soft shadows, likewise HIP only (bind_shadow_extension)
 SHADOW_EXTENSIONS = ("vct_shadow_cones_device", "vct_composite_shadowed_device")
 
+# include/vct_emission.h: emissive surfaces, likewise HIP only (bind_emission_extension)
+EMISSION_EXTENSIONS = ("vct_voxelize_emission", "vct_voxelize_emission_device", "vct_emission_voxels",
+                       "vct_download_emission", "vct_inject_emission", "vct_composite_emissive_device")
+VCT_EMISSION_SCALE_LIMIT = 2.0 ** 111
+
 STATUS = {0: "VCT_OK", 1: "VCT_EINVAL", 2: "VCT_ENOMEM", 3: "VCT_EDEVICE", 4: "VCT_ECOMM", 5: "VCT_ESTATE"}
 
 
@@ -253,6 +258,29 @@ def bind_shadow_extension(lib: C.CDLL, name: str):
     except AttributeError:
         raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
                              "(include/vct_shadow.h is implemented by the HIP library only)") from None
+    fn.restype = res
+    fn.argtypes = args
+    return fn
+
+
+def bind_emission_extension(lib: C.CDLL, name: str):
+    """The include/vct_emission.h function `name` of `lib`, with its signature declared;
+    AttributeError (naming the library) if this implementation does not export it."""
+    P, u32, i32, f32 = C.c_void_p, C.c_uint32, C.c_int32, C.c_float
+    sig = {
+        "vct_voxelize_emission": (i32, [P, P, u32, u32, P, u32, P, P, u32]),
+        "vct_voxelize_emission_device": (i32, [P, P, u32, u32, P, u32, P, P, u32]),
+        "vct_emission_voxels": (i32, [P, C.POINTER(u32)]),
+        "vct_download_emission": (i32, [P, P]),
+        "vct_inject_emission": (i32, [P, f32]),
+        "vct_composite_emissive_device": (i32, [P, P, P, P, P, P, u32, u32, C.POINTER(VctLight), u32, P, f32, P, P]),
+    }
+    res, args = sig[name]
+    try:
+        fn = getattr(lib, name)
+    except AttributeError:
+        raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
+                             "(include/vct_emission.h is implemented by the HIP library only)") from None
     fn.restype = res
     fn.argtypes = args
     return fn
