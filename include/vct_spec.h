@@ -340,4 +340,62 @@
  *    bit. */
 #define VCT_EMISSION_SCALE_LIMIT 2.59614843e33f  /* 2^111 exactly */
 
+/* ---- sky light (vct_sky_cones_device / vct_inject_sky, include/vct_sky.h; no new
+ *      literals) ----------------------------------------------------------------------------
+ * A sky is (up, zenith, horizon, ground): a direction and three colours.
+ *  Input rule.  up: the "K2 input rule" for a direction -- len = sqrtf((ux*ux + uy*uy) + uz*uz)
+ *    in float32 must be finite and > 0 -- and up_n = up / len per component, as
+ *    vct_inject_directional normalises its direction.  Every component of zenith, horizon and
+ *    ground must be finite, have a clear sign bit (-0.0f is refused) and be <= VCT_COLOR_LIMIT
+ *    (the "K2 input rule" for a colour).  Anything else is VCT_EINVAL, with nothing written and
+ *    no state changed.  With |A| < VCT_KD_LIMIT = 2^15 and sum w_k T_k <= ~1 the term
+ *    A * Sk that vct_inject_sky adds stays below 2^15 * 2^105 * ~3 < 2^122, so level 0 stays
+ *    finite (K2's own sum is below 2^127, and below 2^121 for one light).
+ *  Sky(d), for any direction d; branch-free, no fused operation, dot3 of "local lights":
+ *      u     = dot3(d, up_n)
+ *      s_up  = fminf(fmaxf(u, 0.0f), 1.0f)
+ *      s_dn  = fminf(fmaxf(-u, 0.0f), 1.0f)
+ *      Sky_c = (horizon_c + (zenith_c - horizon_c) * s_up) + (ground_c - horizon_c) * s_dn
+ *    d = up_n gives the zenith colour, d = -up_n the ground colour, d perpendicular to up the
+ *    horizon colour; a NaN u gives the horizon colour, since fmaxf(NaN, 0) is 0.
+ *  Receiver: a G-buffer record (P, N) with P.w != 0 -- a pixel of a frame, or a bounce source
+ *    of "light bounces" with its record P_c = g0_c + ((float)x_c + 0.5f) * hh.  The origin o
+ *    and the cone directions d_k are exactly K4's (A.5):
+ *      o_c = (P_c - g0_c) * inv_h + N_c
+ *      sgn = copysignf(1.0f, N.z);  ka = -1.0f / (sgn + N.z);  kb = (N.x * N.y) * ka
+ *      T = (1.0f + ((sgn * N.x) * N.x) * ka,  sgn * kb,  -(sgn * N.x))
+ *      B = (kb,  sgn + (N.y * N.y) * ka,  -N.y)
+ *      d_k,c = (cn_k * N_c + ct_k * T_c) + cb_k * B_c
+ *    over the rows (cn, ct, cb, w) of the context's diffuse cone set: n_diffuse in {1, 9, 16}
+ *    (VCT_CONES1 / 9 / 16), aperture tau = VCT_TAN30 for 1 and 9 cones, VCT_TAN20 for 16.
+ *  Per cone k, in set order:
+ *      a_k = the result of steps 1-5 of "shadow cones" with o, d = d_k, tau and t_lim = +inf
+ *    (so the "light is reached" end never applies).  This is the alpha of K4's own diffuse
+ *    cone k, bit for bit, and the cone takes K4's steps: a sky call counts exactly the cone
+ *    steps of K4's diffuse cones on the same records.
+ *      T_k = fmaxf(1.0f - a_k / VCT_ALPHA_STOP, 0.0f)        (one correctly rounded divide)
+ *  Per receiver, from acc = vis = +0, in set order:
+ *      acc_c = fmaf(w_k * T_k, Sky_c(d_k), acc_c)            (the product w_k * T_k rounded first)
+ *      vis   = fmaf(w_k, T_k, vis)
+ *    Sk = (acc.rgb, vis).  A background record (P.w == 0), and every record of a context with
+ *    n_diffuse = 0, gives +0 in all four channels.
+ *  A non-finite o or d_k (a non-finite position or normal) makes p = o + d t fail the inside
+ *    test of step 1 before the first sample: a_k = +0, T_k = 1, and Sky(d_k) is the horizon
+ *    colour where u is NaN.  No sample is ever taken at a non-finite p.
+ *  The start (o = P' + N, t = 1) is K4's, and K4's self-occlusion on coarse grids comes with
+ *    it ("shadow cones" says the same of its start): a cone that leaves its surface at a
+ *    grazing angle samples the surface's own voxels in its first steps, so on the Cornell
+ *    box at 16^3 and 32^3 about half of the cones saturate and almost none ends with T
+ *    exactly 1.  No other offset is introduced here.
+ *  vct_sky_cones_device: sky4[px] = Sk; with diffuse4_inout, at every valid pixel
+ *      diffuse_c = diffuse_c + Sk_c                          (one add per channel, c = r, g, b)
+ *    and alpha, and every background pixel, untouched.  A diffuse component that is -0.0f
+ *    becomes +0.0f when Sk_c is +0 (an all-zero sky changes no other bit).
+ *  vct_inject_sky: at every bounce source v ("light bounces": occupied, nonzero normal), on
+ *    the level-0 texel of v,
+ *      L_c = L_c + A_c(v) * Sk_c(v)                          (one multiply, then one add; no fma)
+ *    alpha untouched, every other voxel untouched; then the pyramid is rebuilt from that level
+ *    0.  Level 0 stays nonzero exactly at the occupied voxels and every alpha of the pyramid
+ *    is unchanged, so a_k, T_k and vis are the same before and after. */
+
 #endif /* VCT_SPEC_H */

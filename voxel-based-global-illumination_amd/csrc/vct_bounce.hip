@@ -183,6 +183,19 @@ __global__ void __launch_bounds__(256) k_bounce_add(const uint32_t* __restrict__
     pyr[l0_texel(v, n)] = make_float4(L.x + A.x * I.x, L.y + A.y * I.y, L.z + A.z * I.z, L.w);
 }
 
+// sky light: L.rgb = L.rgb + A.rgb * Sk.rgb on level 0 itself (one multiply, one add), L.a kept
+__global__ void __launch_bounds__(256) k_bounce_add_plane(const uint32_t* __restrict__ vox, uint32_t n_src,
+                                                          uint32_t tiles_x, const float4* __restrict__ albedo_occ,
+                                                          const float4* __restrict__ plane, float4* __restrict__ pyr,
+                                                          uint32_t n) {
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    if (s >= n_src) return;
+    const uint32_t v = vox[s];
+    float4* const dst = pyr + l0_texel(v, n);
+    const float4 L = *dst, A = albedo_occ[v], I = plane[bounce_pixel(s, tiles_x)];
+    *dst = make_float4(L.x + A.x * I.x, L.y + A.y * I.y, L.z + A.z * I.z, L.w);
+}
+
 template <typename T>
 hipError_t grow(vct_ctx* c, T*& p, size_t& cap, size_t count) {
     if (cap >= count) return hipSuccess;
@@ -306,6 +319,15 @@ hipError_t launch_bounce_accumulate(vct_ctx* c) {
     hipLaunchKernelGGL(k_bounce_add, dim3((b.n_src + 255u) / 256u), dim3(256), 0, c->stream, (const uint32_t*)b.vox,
                        b.n_src, b.tiles_x, (const float4*)b.l0, (const float4*)c->grid.albedo_occ,
                        (const float4*)(b.gbuf + 2 * b.px_cap), c->grid.pyr, c->grid.n);
+    return hipGetLastError();
+}
+
+hipError_t launch_bounce_add_plane(vct_ctx* c, int plane) {
+    const Bounce& b = c->bounce;
+    if (!b.n_src) return hipSuccess;
+    hipLaunchKernelGGL(k_bounce_add_plane, dim3((b.n_src + 255u) / 256u), dim3(256), 0, c->stream,
+                       (const uint32_t*)b.vox, b.n_src, b.tiles_x, (const float4*)c->grid.albedo_occ,
+                       (const float4*)(b.gbuf + (size_t)plane * b.px_cap), c->grid.pyr, c->grid.n);
     return hipGetLastError();
 }
 

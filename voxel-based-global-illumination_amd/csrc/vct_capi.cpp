@@ -343,6 +343,8 @@ void vct_destroy(vct_ctx* c) {
     if (c->ev) (void)hipEventDestroy(c->ev);
     if (c->xchg_done) (void)hipEventDestroy(c->xchg_done);
     if (c->shadow_done) (void)hipEventDestroy(c->shadow_done);
+    for (hipEvent_t ev : c->sky_ev)
+        if (ev) (void)hipEventDestroy(ev);
     for (auto& en : c->k4tune.e) {
         for (auto& f : en.ev)
             for (auto& sl : f)
@@ -422,7 +424,7 @@ static vct_status voxelize_dev(vct_ctx* c, const void* dv, uint32_t stride, uint
     // if a step below fails part way (K1 has already rewritten the accumulators, the
     // occupied list and level 0 by then): only the success path sets `voxelized` again
     Grid& g = c->grid;
-    g.voxelized = g.injected = g.mipped = g.bounced = g.emitted = false;
+    g.voxelized = g.injected = g.mipped = g.bounced = g.emitted = g.skied = false;
     g.k2_coarse_ok = g.k3_sparse_ok = g.zm_valid = false;
     g.k3_live_bz = 0;
     ++c->grid_epoch;
@@ -478,7 +480,7 @@ static vct_status voxelize_host(vct_ctx* c, const void* verts, uint32_t stride, 
             const float* k = kd4 + 4 * (size_t)m;
             if (!(fabsf(k[0]) < VCT_KD_LIMIT && fabsf(k[1]) < VCT_KD_LIMIT && fabsf(k[2]) < VCT_KD_LIMIT)) {
                 Grid& g = c->grid;
-                g.voxelized = g.injected = g.mipped = g.bounced = g.emitted = false;
+                g.voxelized = g.injected = g.mipped = g.bounced = g.emitted = g.skied = false;
                 g.k2_coarse_ok = g.k3_sparse_ok = g.zm_valid = false;
                 g.k3_live_bz = 0;
                 ++c->grid_epoch;
@@ -597,7 +599,7 @@ vct_status vct_inject_directional(vct_ctx* c, const float dir[3], const float co
     if (st != VCT_OK) return st;
     VCT_HIP(launch_inject(c, lx, ly, lz, color[0], color[1], color[2]), "inject");
     c->grid.injected = true;
-    c->grid.bounced = c->grid.emitted = false;
+    c->grid.bounced = c->grid.emitted = c->grid.skied = false;
     c->grid.mipped = false;
     c->grid.l0_on_peers = false;
     return VCT_OK;
@@ -1006,7 +1008,7 @@ vct_status vct_upload_level0(vct_ctx* c, const float* host) {
     VCT_HIP(launch_relayout(c, (const float4*)tmp, c->grid.pyr, c->grid.n, false), "relayout");
     VCT_HIP(hipStreamSynchronize(c->stream), "sync");
     c->grid.injected = true;
-    c->grid.bounced = c->grid.emitted = false;
+    c->grid.bounced = c->grid.emitted = c->grid.skied = false;
     c->grid.l0_dense = true;
     c->grid.mipped = false;
     c->grid.l0_on_peers = false;
@@ -1020,7 +1022,7 @@ vct_status vct_level0_device(vct_ctx* c, void** dptr, size_t* bytes) {
     if (bytes) *bytes = (size_t)c->grid.n * c->grid.n * c->grid.n * 16;
     // the caller (e.g. an RCCL broadcast) writes level 0 behind our back
     c->grid.injected = true;
-    c->grid.bounced = c->grid.emitted = false;
+    c->grid.bounced = c->grid.emitted = c->grid.skied = false;
     c->grid.l0_dense = true;
     c->grid.mipped = false;
     c->grid.l0_on_peers = false;
@@ -1043,7 +1045,7 @@ vct_status vct_set_level0_from_device(vct_ctx* c, const void* src) {
     const size_t nv = (size_t)c->grid.n * c->grid.n * c->grid.n;
     VCT_HIP(hipMemcpyAsync(c->grid.pyr, src, nv * 16, hipMemcpyDeviceToDevice, c->stream), "copy level0 in");
     c->grid.injected = true;
-    c->grid.bounced = c->grid.emitted = false;
+    c->grid.bounced = c->grid.emitted = c->grid.skied = false;
     c->grid.l0_dense = true;
     c->grid.mipped = false;
     c->grid.l0_on_peers = false;

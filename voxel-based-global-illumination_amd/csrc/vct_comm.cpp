@@ -217,7 +217,7 @@ vct_status vct_comm_broadcast_level0(vct_ctx* c, uint32_t root) {
              "ncclBroadcast level 0");
     if (!is_root) {
         c->grid.injected = true;
-        c->grid.bounced = c->grid.emitted = false;
+        c->grid.bounced = c->grid.emitted = c->grid.skied = false;
         c->grid.l0_dense = true;    // replaced densely: the next K2 clears it whole
     }
     c->grid.mipped = false;

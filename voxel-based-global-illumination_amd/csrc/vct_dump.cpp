@@ -141,7 +141,7 @@ struct InvalidateOnFail {
     ~InvalidateOnFail() {
         if (!armed) return;
         Grid& g = c->grid;
-        g.voxelized = g.injected = g.mipped = g.bounced = g.emitted = false;
+        g.voxelized = g.injected = g.mipped = g.bounced = g.emitted = g.skied = false;
         g.k2_coarse_ok = g.k3_sparse_ok = g.zm_valid = false;
         ++c->grid_epoch;
     }
@@ -187,7 +187,7 @@ vct_status vct_load_grid(vct_ctx* c, const char* stem) {
         }
         // what a voxelization invalidates (voxelize_dev), then K1's state written back
         guard.armed = true;
-        g.voxelized = g.injected = g.mipped = g.bounced = g.emitted = false;
+        g.voxelized = g.injected = g.mipped = g.bounced = g.emitted = g.skied = false;
         g.k2_coarse_ok = g.k3_sparse_ok = g.zm_valid = false;
         g.k3_live_bz = 0;
         ++c->grid_epoch;

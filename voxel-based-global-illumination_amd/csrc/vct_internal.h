@@ -78,6 +78,7 @@ struct Grid {
     bool l0_on_peers = false;   // multi-device: the other devices hold this level 0 (vct_build_mips copies it)
     bool bounced = false;       // vct_inject_bounces has added to this level 0 (cleared with every new level 0)
     bool emitted = false;       // vct_inject_emission has added to this level 0 (cleared where bounced is)
+    bool skied = false;         // vct_inject_sky has added to this level 0 (cleared where bounced is)
 };
 
 // Emissive surfaces (vct_emission.hip; vct_spec.h "emissive surfaces").  The emission grid
@@ -267,6 +268,10 @@ struct vct_ctx {
     hipEvent_t shadow_done = nullptr;
     hipStream_t shadow_stream = nullptr;
     int shadow_path = 0;                     // address path of the last march: 32 or 64 (vct_debug_shadow_path)
+    int sky_path = 0;                        // the same of the last sky march (vct_debug_sky_path)
+    bool sky_profile = false;                // vct_debug_sky: time the stages of vct_inject_sky with events
+    hipEvent_t sky_ev[4] = {};
+    float sky_ms[3] = {0, 0, 0};             // march, add and K3 of the last vct_inject_sky
     vct::StreamScratch k4s[vct::kStreamSets];   // K4 hand-over + reorder scratch per stream (k4_scratch)
     vct::K4Tuner k4tune;                // timed-form choice of the default cone trace
     vct::Bounce bounce;                 // source list of vct_inject_bounces
@@ -352,6 +357,9 @@ hipError_t bounce_sources(vct_ctx* c);
 hipError_t launch_bounce_save(vct_ctx* c);
 hipError_t launch_bounce_gather(vct_ctx* c);
 hipError_t launch_bounce_accumulate(vct_ctx* c);
+// sky light (vct_sky.hip): level 0 += A * Sk at every source, Sk read from the source
+// G-buffer's plane `plane` (2 or 3: K4's outputs, free between bounces)
+hipError_t launch_bounce_add_plane(vct_ctx* c, int plane);
 void bounce_free(vct_ctx* c);
 // emissive surfaces (vct_emission.hip): the context's emission grid is the one built for the
 // current voxelization, and may hold an emissive voxel; release with the context

@@ -421,7 +421,7 @@ extern "C" vct_status vct_inject_lights(vct_ctx* c, const vct_light* lights, uin
         e = launch_lights(c, dl, n_lights);
     if (e != hipSuccess) return lhip(c, e, "inject_lights");
     c->grid.injected = true;
-    c->grid.bounced = c->grid.emitted = false;
+    c->grid.bounced = c->grid.emitted = c->grid.skied = false;
     c->grid.mipped = false;
     c->grid.l0_on_peers = false;
     return VCT_OK;

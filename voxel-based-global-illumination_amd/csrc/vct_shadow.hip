@@ -27,27 +27,24 @@
 // n <= 512: every level is bound as a buffer resource (base at the first texel's .w), so
 // the spec's zero border is the hardware range check.  n = 1024 (and vct_debug_shadow's
 // force64): 64-bit addresses and an explicit select.
+//
+// The march itself (the step rows a wave holds, the alpha sample with both address paths,
+// the lockstep cone) is csrc/vct_alpha_march.h, shared with vct_sky.hip; this unit keeps the
+// context's table set (ks_steps, step_tables, tables_enter / tables_leave), which the sky
+// calls go through as well.
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <cmath>
 #include <cstring>
 #include "vct_internal.h"
 #include "vct_light_terms.h"
+#include "vct_alpha_march.h"
 
 namespace vct {
 namespace {
 
-// rows per step table, the +inf sentinel included: VCT_SPEC_TAU_MIN on 1024^3 needs 265
-constexpr int kShadowRows = 320;
 constexpr int kSlotTabs = 10;            // vct_ctx::scratch
-constexpr uint32_t kHard = 0xffu;        // ShadowK::slot of a light with tan_half 0
-constexpr uint32_t kOutT = 0x0fffffffu;  // texel index of a corner outside its level: << 4 is past any level
-
-struct alignas(16) AlphaRange {
-    const float* base;           // &level[0].w
-    uint32_t bytes;              // from there to the level's end (every face); 0: not bound (64-bit path)
-    uint32_t pad;
-};
+constexpr uint32_t kHard = kHardSlot;    // ShadowK::slot of a light with tan_half 0
 
 struct ShadowK {
     const float4* pos;
@@ -88,125 +85,6 @@ __global__ void __launch_bounds__(64) ks_steps(const StepsK k) {
         rows[i] = StepRow{t, D, m - (float)l0, l0};
         t = t + VCT_STEP_SCALE * D;
     }
-}
-
-// coordinates c and c + 1 of one axis of a level of nl = 2^lg texels, as OR-able fields of
-// the brick layout's texel index (vct_device.h texel_index): (c >> 1) << sh | (c & 1) << bit
-struct Axis {
-    uint32_t t0, t1;
-    bool in0, in1;
-};
-__device__ __forceinline__ Axis axis_fields(int c, uint32_t nl, uint32_t sh, uint32_t bit) {
-    const uint32_t u = (uint32_t)c, v = u + 1u;
-    return Axis{((u >> 1) << sh) | ((u & 1u) << bit), ((v >> 1) << sh) | ((v & 1u) << bit), u < nl, v < nl};
-}
-
-// the alpha of D_l(p, d) (A.5) for a wave-uniform level l; `act`: the lane still marches (an
-// ended lane reads nothing).  fx, fy, fz: the faces d selects; wdx, wdy, wdz: d_c^2.
-template <bool O32>
-__device__ __forceinline__ float sample_alpha(const ShadowK& k, int l, bool act, float px, float py, float pz, int fx,
-                                              int fy, int fz, float wdx, float wdy, float wdz) {
-    const float scale = __uint_as_float((uint32_t)(127 - l) << 23);   // 2^-l, exact
-    const float cx = px * scale - 0.5f, cy = py * scale - 0.5f, cz = pz * scale - 0.5f;
-    const float flx = floorf(cx), fly = floorf(cy), flz = floorf(cz);
-    const float ax = cx - flx, ay = cy - fly, az = cz - flz;
-    const float wx[2] = {1.0f - ax, ax}, wy[2] = {1.0f - ay, ay}, wz[2] = {1.0f - az, az};
-    const uint32_t lg = (uint32_t)(k.lgn - l), lnb = lg > 0u ? lg - 1u : 0u, nl = 1u << lg;
-    const Axis X = axis_fields((int)flx, nl, 3u, 0u), Y = axis_fields((int)fly, nl, lnb + 3u, 1u),
-               Z = axis_fields((int)flz, nl, 2u * lnb + 3u, 2u);
-    const bool faces = l != 0 && k.aniso;
-    const uint32_t shf = 3u * lg;                                      // face f starts at texel f << shf
-    const AlphaRange r = k.lvl[l];
-    float acc = 0.0f;
-    if constexpr (O32) {
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)r.base, (short)0, (int)r.bytes, 0x00020000);
-        const uint32_t xs[2] = {act && X.in0 ? X.t0 : kOutT, act && X.in1 ? X.t1 : kOutT};
-        const uint32_t ys[2] = {Y.in0 ? Y.t0 : kOutT, Y.in1 ? Y.t1 : kOutT};
-        const uint32_t zs[2] = {Z.in0 ? Z.t0 : kOutT, Z.in1 ? Z.t1 : kOutT};
-        const auto ld = [&](uint32_t texel) {
-            return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, texel << 4, 0, 0));
-        };
-        if (!faces) {
-            float v[8];
-#pragma unroll
-            for (int c = 0; c < 8; ++c) v[c] = ld(xs[c & 1] | ys[(c >> 1) & 1] | zs[c >> 2]);
-#pragma unroll
-            for (int c = 0; c < 8; ++c) acc = fmaf((wx[c & 1] * wy[(c >> 1) & 1]) * wz[c >> 2], v[c], acc);
-            return acc;
-        }
-        const uint32_t FX = (uint32_t)fx << shf, FY = (uint32_t)fy << shf, FZ = (uint32_t)fz << shf;
-        float vx[8], vy[8], vz[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const uint32_t t = xs[c & 1] | ys[(c >> 1) & 1] | zs[c >> 2];
-            vx[c] = ld(t | FX);
-            vy[c] = ld(t | FY);
-            vz[c] = ld(t | FZ);
-        }
-#pragma unroll
-        for (int c = 0; c < 8; ++c)
-            acc = fmaf((wx[c & 1] * wy[(c >> 1) & 1]) * wz[c >> 2], fmaf(wdz, vz[c], fmaf(wdy, vy[c], wdx * vx[c])), acc);
-        return acc;
-    } else {
-        const float* const base = r.base;
-        const auto ld = [&](uint32_t texel, bool in) {
-            const float v = base[(size_t)(in ? texel : 0u) << 2];
-            return in ? v : 0.0f;
-        };
-        const uint32_t xs[2] = {X.t0, X.t1}, ys[2] = {Y.t0, Y.t1}, zs[2] = {Z.t0, Z.t1};
-        const bool ix[2] = {act && X.in0, act && X.in1}, iy[2] = {Y.in0, Y.in1}, iz[2] = {Z.in0, Z.in1};
-        const uint32_t FX = faces ? (uint32_t)fx << shf : 0u, FY = (uint32_t)fy << shf, FZ = (uint32_t)fz << shf;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const uint32_t t = xs[c & 1] | ys[(c >> 1) & 1] | zs[c >> 2];
-            const bool in = ix[c & 1] && iy[(c >> 1) & 1] && iz[c >> 2];
-            float v = ld(t | FX, in);
-            if (faces) v = fmaf(wdz, ld(t | FZ, in), fmaf(wdy, ld(t | FY, in), wdx * v));
-            acc = fmaf((wx[c & 1] * wy[(c >> 1) & 1]) * wz[c >> 2], v, acc);
-        }
-        return acc;
-    }
-}
-
-__device__ __forceinline__ float lane_row(float v, int r) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), r));
-}
-
-// one shadow cone per lane, the wave in lockstep ("shadow cones" 1-5); returns a.
-// `need`: the lane marches at all.  The direction is per lane; for a directional light the
-// caller passes the light's own (scalar) l, and the faces and d^2 below stay scalar.
-template <bool O32>
-__device__ __forceinline__ float cone(const ShadowK& k, const StepRow* __restrict__ tab, bool need, float ox, float oy,
-                                      float oz, float dx, float dy, float dz, float t_lim, uint32_t& steps) {
-    const float nf = (float)k.n;
-    const int fx = dx >= 0.0f ? VCT_FACE_PX : VCT_FACE_NX;
-    const int fy = dy >= 0.0f ? VCT_FACE_PY : VCT_FACE_NY;
-    const int fz = dz >= 0.0f ? VCT_FACE_PZ : VCT_FACE_NZ;
-    const float wdx = dx * dx, wdy = dy * dy, wdz = dz * dz;
-    float a = 0.0f;
-    bool act = need;
-    StepRow row{};
-    for (int i = 0; i < kShadowRows; ++i) {
-        const int r = i & 63;
-        if (r == 0) row = tab[i + (int)threadIdx.x];          // rows i .. i + 63, lane r keeps row i + r
-        const float t = lane_row(row.t, r);
-        if (!(t <= k.tmax)) break;                             // the sentinel: every lane ends
-        const float px = ox + dx * t, py = oy + dy * t, pz = oz + dz * t;
-        act = act & (a < VCT_ALPHA_STOP) & !(t >= t_lim) &
-              ((px >= 0.0f) & (px <= nf) & (py >= 0.0f) & (py <= nf) & (pz >= 0.0f) & (pz <= nf));
-        if (__builtin_amdgcn_ballot_w64(act) == 0ull) break;
-        const int l0 = __builtin_amdgcn_readlane(row.l0, r);
-        const float fr = lane_row(row.fr, r);
-        float s = sample_alpha<O32>(k, l0, act, px, py, pz, fx, fy, fz, wdx, wdy, wdz);
-        if (fr > 0.0f && l0 < k.L) {
-            const float s1 = sample_alpha<O32>(k, l0 + 1, act, px, py, pz, fx, fy, fz, wdx, wdy, wdz);
-            s = fmaf(fr, s1, (1.0f - fr) * s);
-        }
-        const float oma = 1.0f - a;
-        a = act ? fmaf(oma, s, a) : a;
-        steps += act ? 1u : 0u;
-    }
-    return a;
 }
 
 template <bool O32>
@@ -302,12 +180,12 @@ int table_rows(float tau, float tmax) {
     return t <= tmax ? kShadowRows + 1 : i + 1;
 }
 
-// slot[j] = the step table of light j's aperture (kHard for tan_half 0), building what the
-// context does not hold yet.  A table is never rewritten while the context keeps it; when
-// the 64 slots are used up, the set starts again from this call's apertures.  The caller has
-// ordered the ctx stream after the previous call's march (tables_enter), so both the build
-// and the restart are safe whatever streams the calls come on.
-vct_status step_tables(vct_ctx* c, const float* tan_half, uint32_t n_lights, uint8_t* slot, const StepRow** tabs) {
+}  // namespace
+
+// the context's step tables (vct_alpha_march.h has the contract)
+vct_status step_tables(vct_ctx* c, const char* what, const float* tan_half, uint32_t n_lights, uint8_t* slot,
+                       const StepRow** tabs) {
+    const std::string where = std::string(what) + ": step tables";
     const Grid& g = c->grid;
     const float tmax = (float)g.n * VCT_SQRT3;
     float tau[VCT_MAX_LIGHTS];
@@ -315,7 +193,7 @@ vct_status step_tables(vct_ctx* c, const float* tan_half, uint32_t n_lights, uin
         tau[j] = tan_half[j] == 0.0f ? 0.0f : fminf(fmaxf(tan_half[j], VCT_SPEC_TAU_MIN), VCT_SPEC_TAU_MAX);
     void* p = nullptr;
     hipError_t e = scratch_get(c, kSlotTabs, sizeof(StepRow) * kShadowRows * VCT_MAX_LIGHTS, &p);
-    if (e != hipSuccess) return lhip(c, e, "shadow_cones: step tables");
+    if (e != hipSuccess) return lhip(c, e, where.c_str());
     *tabs = (const StepRow*)p;
     for (int pass = 0; pass < 2; ++pass) {
         uint32_t have = c->shadow_taus, first = have;
@@ -328,7 +206,7 @@ vct_status step_tables(vct_ctx* c, const float* tan_half, uint32_t n_lights, uin
             if (s == have) {
                 if (have == VCT_MAX_LIGHTS) { fits = false; break; }
                 if (table_rows(tau[j], tmax) > kShadowRows)
-                    return lfail(c, VCT_EINVAL, "shadow_cones: the aperture needs more step rows than a table holds");
+                    return lfail(c, VCT_EINVAL, std::string(what) + ": the aperture needs more step rows than a table holds");
                 c->shadow_tau[have++] = tau[j];
             }
             slot[j] = (uint8_t)s;
@@ -345,16 +223,16 @@ vct_status step_tables(vct_ctx* c, const float* tan_half, uint32_t n_lights, uin
             sk.tmax = tmax; sk.Lf = (float)g.L;
             sk.tabs = (StepRow*)p;
             hipLaunchKernelGGL(ks_steps, dim3(1), dim3(64), 0, c->stream, sk);
-            if ((e = hipGetLastError()) != hipSuccess) return lhip(c, e, "shadow_cones: step tables");
+            if ((e = hipGetLastError()) != hipSuccess) return lhip(c, e, where.c_str());
             c->shadow_taus = have;
         }
         return VCT_OK;
     }
-    return lfail(c, VCT_EINVAL, "shadow_cones: step tables");
+    return lfail(c, VCT_EINVAL, where);
 }
 
-// Order this call after the previous vct_shadow_cones_device of the context when that one was
-// queued on another stream (vct_ctx::shadow_done), and mark this call's end.
+// Order this call after the context's previous march over the tables (a shadow or a sky call)
+// when that one was queued on another stream (vct_ctx::shadow_done), and mark this call's end.
 hipError_t tables_enter(vct_ctx* c) {
     if (c->shadow_done && c->shadow_stream != c->stream) return hipStreamWaitEvent(c->stream, c->shadow_done, 0);
     return hipSuccess;
@@ -369,7 +247,6 @@ hipError_t tables_leave(vct_ctx* c) {
     return hipEventRecord(c->shadow_done, c->stream);
 }
 
-}  // namespace
 }  // namespace vct
 
 using namespace vct;
@@ -401,13 +278,9 @@ extern "C" vct_status vct_shadow_cones_device(vct_ctx* c, const float* pos4, con
     ShadowK k;
     std::memset(&k, 0, sizeof k);
     if ((e = tables_enter(c)) != hipSuccess) return lhip(c, e, "shadow_cones: stream wait");
-    if ((st = step_tables(c, tan_half, n_lights, k.slot, &k.tabs)) != VCT_OK) return st;
+    if ((st = step_tables(c, "shadow_cones", tan_half, n_lights, k.slot, &k.tabs)) != VCT_OK) return st;
     const bool o32 = g.n <= 512 && !g_force64.load();
-    for (int i = 0; i <= (int)g.L; ++i) {
-        const uint64_t ni = (uint64_t)(g.n >> i);
-        const uint64_t by = ni * ni * ni * 16u * (i > 0 && g.aniso ? 6u : 1u);
-        k.lvl[i] = AlphaRange{(const float*)(g.pyr + g.lvl_off[i]) + 3, o32 ? (uint32_t)(by - 12u) : 0u, 0u};
-    }
+    alpha_ranges(g, o32, k.lvl);
     k.pos = (const float4*)pos4; k.nrm = (const float4*)nrm4;
     k.bits = g.occ_bits;
     k.vis = vis; k.steps_total = cone_steps;

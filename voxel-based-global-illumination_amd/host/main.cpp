@@ -5,7 +5,7 @@
 //
 //   vct_headless <model.obj> [grid=256] [width=800] [height=600] [frames=5] [out.ppm] [devices=1]
 //                [--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32]
-//                [--light SPEC]... [--shadow-tan T]
+//                [--light SPEC]... [--shadow-tan T] [--sky Z[:H[:G]]]
 //   (devices > 1: one process drives that many GPUs through vct_create_multi)
 //   --model: the model matrix of the reference's draw, T(0,-1.75,0) S(0.2)
 //            (r_voxelization.cpp:26-29; default), or none;
@@ -17,6 +17,9 @@
 //   --shadow-tan: T > 0 shades the direct term with shadow cones of half-angle tangent T toward
 //            every light of the frame (include/vct_shadow.h) instead of the hard voxel walk;
 //            0 (the default) keeps the walk;
+//   --sky:    a sky (include/vct_sky.h) with up = +y: Z, H and G are the r,g,b of the zenith, the
+//            horizon (default: Z) and the ground (default: 0,0,0).  It is injected per voxel
+//            after the mips and before the bounces, and added per pixel to the diffuse term;
 //   --light:  one light of a light list (include/vct_lights.h), repeatable, in list order; with
 //            any --light the list replaces the default directional light.  SPEC is colon-
 //            separated fields of comma-separated floats, world units, angles in degrees:
@@ -83,6 +86,36 @@ static bool parse_light(const std::string& spec, vct_light* out) {
     return true;
 }
 
+// one --sky Z[:H[:G]] (see above) -> *out with up = +y; false: malformed (a field that is not
+// three numbers, more than three fields, a negative or non-finite component)
+static bool parse_sky(const std::string& spec, vct_sky* out) {
+    float c[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+    size_t at = 0;
+    int k = 0;
+    for (; at <= spec.size(); ++k) {
+        if (k == 3) return false;
+        const size_t end = std::min(spec.find(':', at), spec.size());
+        const std::string field = spec.substr(at, end - at);
+        at = end + 1;
+        const char* p = field.c_str();
+        for (int j = 0; j < 3; ++j) {
+            char* q = nullptr;
+            c[k][j] = std::strtof(p, &q);
+            if (q == p || *q != (j < 2 ? ',' : '\0')) return false;
+            if (!std::isfinite(c[k][j]) || std::signbit(c[k][j])) return false;
+            p = q + 1;
+        }
+    }
+    *out = vct_sky{};
+    out->up[1] = 1.0f;
+    for (int j = 0; j < 3; ++j) {
+        out->zenith[j] = c[0][j];
+        out->horizon[j] = k > 1 ? c[1][j] : c[0][j];
+        out->ground[j] = k > 2 ? c[2][j] : 0.0f;
+    }
+    return true;
+}
+
 int main(int argc, char** argv) {
     std::vector<std::string> pos;
     bool ref_model = true, fit_grid = true;
@@ -90,6 +123,8 @@ int main(int argc, char** argv) {
     std::string linear;
     std::vector<vct_light> lights;
     float shadow_tan = 0.0f;
+    bool has_sky = false;
+    vct_sky sky{};
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--model=reference") ref_model = true;
@@ -107,12 +142,17 @@ int main(int argc, char** argv) {
             if (!parse_light(spec, &l)) { std::fprintf(stderr, "malformed --light %s\n", spec.c_str()); return 2; }
             lights.push_back(l);
         }
+        else if ((a == "--sky" && i + 1 < argc) || a.rfind("--sky=", 0) == 0) {
+            const std::string spec = a == "--sky" ? argv[++i] : a.substr(6);
+            if (!parse_sky(spec, &sky)) { std::fprintf(stderr, "malformed --sky %s\n", spec.c_str()); return 2; }
+            has_sky = true;
+        }
         else if (a.rfind("--", 0) == 0) { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
         else pos.push_back(a);
     }
     if (pos.empty()) {
         std::fprintf(stderr, "usage: %s model.obj [grid] [width] [height] [frames] [out.ppm] [devices] "
-                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] "
+                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] [--sky Z[:H[:G]]] "
                              "[--light dir:d:rgb | point:p:rgb:range | spot:p:d:rgb:range:inner:outer]...\n",
                      argv[0]);
         return 2;
@@ -130,6 +170,8 @@ int main(int argc, char** argv) {
     s.bounces = (uint32_t)bounces;
     s.shadow_tan = shadow_tan;
     s.lights = lights;
+    s.has_sky = has_sky;
+    s.sky = sky;
     if (ref_model) ReferenceModelMatrix(s.model);
 
     AssetsManager& A = AssetsManager::Instance();            // assets.cpp:22-45

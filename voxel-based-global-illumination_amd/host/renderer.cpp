@@ -37,6 +37,7 @@ ConeTraceRenderer::~ConeTraceRenderer() {
     for (void* p : out_) vct_device_free(ctx_, p);
     vct_device_free(ctx_, counter_);
     if (vis_) vct_device_free(ctx_, vis_);
+    if (sky_) vct_device_free(ctx_, sky_);
     vct_destroy(ctx_);
 }
 
@@ -74,6 +75,7 @@ bool ConeTraceRenderer::rebuild_scene() {
         return false;
     }
     if (!check(vct_build_mips(ctx_), "vct_build_mips")) return false;
+    if (s_.has_sky && !check(vct_inject_sky(ctx_, &s_.sky), "vct_inject_sky")) return false;
     if (s_.bounces && !check(vct_inject_bounces(ctx_, s_.bounces), "vct_inject_bounces")) return false;
     scene_dirty_ = false;
     return true;
@@ -105,6 +107,11 @@ void ConeTraceRenderer::Render() {
     if (!check(vct_synchronize(ctx_), "sync")) return;
     last_ms_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     check(vct_memcpy(ctx_, &last_steps_, counter_, 8, 1), "read counter");
+    if (s_.has_sky) {   // the sky into the diffuse plane, once per frame, before whichever composite reads it
+        if (!sky_ && !check(vct_device_alloc(ctx_, (size_t)s_.width * s_.height * 16, &sky_), "alloc sky plane")) return;
+        check(vct_sky_cones_device(ctx_, a.pos4, a.nrm4, s_.width, s_.height, &s_.sky, (float*)sky_, a.diffuse4, nullptr),
+              "vct_sky_cones_device");
+    }
 }
 
 vct_status ConeTraceRenderer::composite(float* lin, uint32_t* rgba) {

@@ -42,6 +42,11 @@ struct ConeTraceSettings {
     // > 0: the composite's direct term is shadowed by cones of this half-angle tangent toward
     // every light of the frame (include/vct_shadow.h) instead of the hard voxel walk; 0: the walk
     float shadow_tan = 0.0f;
+    // a sky (include/vct_sky.h): injected per voxel after the mips and before the bounces
+    // (vct_inject_sky), and added per pixel to the diffuse plane after K4 (vct_sky_cones_device),
+    // so every composite shows it through albedo x diffuse
+    bool has_sky = false;
+    vct_sky sky = {{0.0f, 1.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
     // model matrix applied to the model's vertices before K1, column-major; main.cpp
     // sets the reference's T(0,-1.75,0) S(0.2) (r_voxelization.cpp:26-29) by default
     float model[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
@@ -77,6 +82,7 @@ private:
     void* counter_ = nullptr;
     void* vis_ = nullptr;                 // V planes of the soft-shadow composite (shadow_tan > 0), kept
     size_t vis_bytes_ = 0;
+    void* sky_ = nullptr;                 // (Sk.rgb, vis) plane of the frame's sky call (has_sky), kept
     bool scene_dirty_ = true;
     vct_status status_ = VCT_OK;
     std::string error_;

@@ -28,10 +28,11 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import VCT_ALL_RANKS, VctCamera, VctCommId, VctConfig, VctLight, VctTexture, VctTraceArgs
+from ._lib import VCT_ALL_RANKS, VctCamera, VctCommId, VctConfig, VctLight, VctSky, VctTexture, VctTraceArgs
 
 __all__ = ["Context", "VctError", "VctConfig", "VctCamera", "tiles_for_rank", "tile_offset", "VERTEX_FLOATS",
-           "VCT_ALL_RANKS", "comm_frame_layout", "VctLight", "directional_light", "point_light", "spot_light"]
+           "VCT_ALL_RANKS", "comm_frame_layout", "VctLight", "directional_light", "point_light", "spot_light",
+           "VctSky", "sky_light"]
 
 VERTEX_FLOATS = 14          # reference Vertex: Position, Normal, TexCoords, Tangent, Bitangent
 VERTEX_STRIDE = VERTEX_FLOATS * 4
@@ -80,6 +81,16 @@ def spot_light(position, direction, color=(1.0, 1.0, 1.0), range: float = 1.0, i
     l.cos_inner = float(np.cos(np.deg2rad(np.float32(inner_deg)))) if cos_inner is None else float(cos_inner)
     l.cos_outer = float(np.cos(np.deg2rad(np.float32(outer_deg)))) if cos_outer is None else float(cos_outer)
     return l
+
+
+def sky_light(zenith, horizon=None, ground=None, up=(0.0, 1.0, 0.0)) -> VctSky:
+    """A vct_sky: the colours straight up, at the horizon (default: the zenith's) and straight
+    down (default: black), blended by the cosine to `up`."""
+    s = VctSky()
+    s.up, s.zenith = _f3(up), _f3(zenith)
+    s.horizon = _f3(zenith if horizon is None else horizon)
+    s.ground = _f3((0.0, 0.0, 0.0) if ground is None else ground)
+    return s
 
 
 def _light_array(lights):
@@ -563,6 +574,29 @@ class Context:
             self._dev(vis, "vis", _F32, nl * width * height), float(scale),
             self._dev(out_linear4, "out_linear4", _F32, n),
             self._dev(out_rgba8, "out_rgba8", _I32, width * height)), "composite_emissive")
+
+    # -- sky light (include/vct_sky.h) --------------------------------------
+    def sky_cones_device(self, pos4, nrm4, width, height, sky, sky4, diffuse4_inout=None, cone_steps=None):
+        """vct_sky_cones_device: (Sk.rgb, vis) per pixel into sky4, a float32 device tensor
+        [height, width, 4]; diffuse4_inout (K4's diffuse plane of the frame): rgb += Sk.rgb at
+        every valid pixel.  sky: a VctSky (vct.sky_light).  cone_steps: a 1-element int64
+        device tensor that the call adds its cone steps to."""
+        fn = _lib.bind_sky_extension(self.lib, "vct_sky_cones_device")
+        if not isinstance(sky, VctSky):
+            raise VctError(_EINVAL, f"sky_cones: expected a VctSky (vct.sky_light), got {type(sky).__name__}")
+        n = 4 * width * height
+        self._check(fn(self.h, self._dev(pos4, "pos4", _F32, n), self._dev(nrm4, "nrm4", _F32, n), width, height,
+                       C.byref(sky), self._dev(sky4, "sky4", _F32, n),
+                       self._dev(diffuse4_inout, "diffuse4_inout", _F32, n),
+                       self._dev(cone_steps, "cone_steps", _I64, 1)), "sky_cones")
+
+    def inject_sky(self, sky):
+        """vct_inject_sky: level 0 += A * Sk at every bounce source, then the mips (after
+        build_mips, before inject_bounces).  Once per level 0: VctError(ESTATE) on a second call."""
+        fn = _lib.bind_sky_extension(self.lib, "vct_inject_sky")
+        if not isinstance(sky, VctSky):
+            raise VctError(_EINVAL, f"inject_sky: expected a VctSky (vct.sky_light), got {type(sky).__name__}")
+        self._check(fn(self.h, C.byref(sky)), "inject_sky")
 
     # -- grid access ------------------------------------------------------
     def download_level(self, level: int, face: int = 0) -> np.ndarray:

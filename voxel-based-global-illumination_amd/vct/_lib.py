@@ -47,6 +47,9 @@ EMISSION_EXTENSIONS = ("vct_voxelize_emission", "vct_voxelize_emission_device", 
                        "vct_download_emission", "vct_inject_emission", "vct_composite_emissive_device")
 VCT_EMISSION_SCALE_LIMIT = 2.0 ** 111
 
+# include/vct_sky.h: sky light, likewise HIP only (bind_sky_extension)
+SKY_EXTENSIONS = ("vct_sky_cones_device", "vct_inject_sky")
+
 STATUS = {0: "VCT_OK", 1: "VCT_EINVAL", 2: "VCT_ENOMEM", 3: "VCT_EDEVICE", 4: "VCT_ECOMM", 5: "VCT_ESTATE"}
 
 
@@ -88,6 +91,15 @@ class VctLight(C.Structure):          # vct_light, 60 bytes
         ("cos_inner", C.c_float),
         ("cos_outer", C.c_float),
         ("reserved", C.c_uint32 * 2),
+    ]
+
+
+class VctSky(C.Structure):            # vct_sky, 48 bytes
+    _fields_ = [
+        ("up", C.c_float * 3),
+        ("zenith", C.c_float * 3),
+        ("horizon", C.c_float * 3),
+        ("ground", C.c_float * 3),
     ]
 
 
@@ -284,6 +296,47 @@ def bind_emission_extension(lib: C.CDLL, name: str):
     fn.restype = res
     fn.argtypes = args
     return fn
+
+
+def bind_sky_extension(lib: C.CDLL, name: str):
+    """The include/vct_sky.h function `name` of `lib`, with its signature declared;
+    AttributeError (naming the library) if this implementation does not export it."""
+    P, u32, i32 = C.c_void_p, C.c_uint32, C.c_int32
+    sig = {
+        "vct_sky_cones_device": (i32, [P, P, P, u32, u32, C.POINTER(VctSky), P, P, P]),
+        "vct_inject_sky": (i32, [P, C.POINTER(VctSky)]),
+    }
+    res, args = sig[name]
+    try:
+        fn = getattr(lib, name)
+    except AttributeError:
+        raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
+                             "(include/vct_sky.h is implemented by the HIP library only)") from None
+    fn.restype = res
+    fn.argtypes = args
+    return fn
+
+
+def debug_sky(lib: C.CDLL, handle=None, force64: int = -1, profile: int = -1):
+    """Test and tool hook (vct_debug_sky, not part of the headers).  force64 >= 0, process-wide:
+    nonzero sends every grid's sky march through the 64-bit-address path (the one 1024^3
+    takes).  profile >= 0: nonzero times the stages of the context's following inject_sky
+    calls.  -> (march, add, K3) ms of the last timed inject_sky."""
+    fn = lib.vct_debug_sky
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
+    ms = (C.c_float * 3)()
+    fn(handle, int(force64), int(profile), ms)
+    return tuple(float(v) for v in ms)
+
+
+def debug_sky_path(lib: C.CDLL, handle) -> int:
+    """Test hook (vct_debug_sky_path): the address path the context's last sky march was
+    launched with -- 32 (buffer resources), 64 (64-bit addresses), 0 before any."""
+    fn = lib.vct_debug_sky_path
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p]
+    return int(fn(handle))
 
 
 def debug_shadow(lib: C.CDLL, force64: bool = False):
