@@ -398,4 +398,36 @@
  *    0.  Level 0 stays nonzero exactly at the occupied voxels and every alpha of the pyramid
  *    is unchanged, so a_k, T_k and vis are the same before and after. */
 
+/* ---- dynamic layer (vct_voxelize_dynamic*, include/vct_dynamic.h; no new arithmetic) ----
+ *  The context holds at most one dynamic layer: a set of triangles on top of the static
+ *    grid, the grid of the last successful vct_voxelize* (or vct_load_grid).  Let S be the
+ *    static mesh and D the layer's.  union(S, D) is the mesh of S's vertices followed by D's,
+ *    S's triangles followed by D's (D's vertex indices offset by S's vertex count), S's
+ *    materials followed by D's (D's material ids offset by S's material count).
+ *  Equality: after vct_voxelize_dynamic*(D) the context is, bit for bit, the context after
+ *    vct_voxelize(union(S, D)): K1's sums and counts, albedo / occupancy and normals, the
+ *    occupancy bits, the set of occupied voxels, and therefore everything computed from them
+ *    (level 0 of every vct_inject_*, every mip face, K4, the shadow and sky marches, the
+ *    bounce sources, every composite), and both G-buffer passes (S's triangles then D's, in
+ *    that index order: ties go to the lower index).  This holds after any sequence of
+ *    updates, because S_union(v) = S_S(v) + S_D(v) and count_union(v) = count_S(v) +
+ *    count_D(v) are sums of integers: an update subtracts the previous layer's terms and adds
+ *    the new layer's, modulo 2^64, exactly.  n_idx == 0 removes the layer: the grid is S's.
+ *  A voxel only the removed layer occupied: an all-zero record, albedo = normal = (0,0,0,0),
+ *    a +0 level-0 texel, a clear occupancy bit, absent from the occupied list.  Records are
+ *    zero everywhere outside the occupancy.
+ *  Input rule: K1's ("K1 input rule"): a finite vertex anywhere is legal; a triangle with a
+ *    non-finite voxel-unit vertex is skipped (no candidates, a zero triangle for the G-buffer
+ *    passes); Kd must be finite with |Kd| < VCT_KD_LIMIT.  The layer takes Kd materials only.
+ *  Packed sums: while the grid's records are packed ("K1", two sums per word), a voxel the
+ *    update touched must keep count x max|value| < 2^31 with max|value| the larger of the
+ *    static pass's and the layer's; otherwise the occupied records are converted in place to
+ *    one sum per word and the layer is added in that form.  The sums, and so every result,
+ *    are the same either way.
+ *  State: a new vct_voxelize* or vct_load_grid drops the layer record; what it leaves is the
+ *    static grid.  vct_save_grid with a layer in place saves the union as a plain grid.
+ *  The call invalidates what a voxelization invalidates: level 0, the mips, bounces,
+ *    emission and sky marks, the emission grid and the bounce source list; vct_inject_*
+ *    and vct_build_mips (a full build) follow it as they follow vct_voxelize. */
+
 #endif /* VCT_SPEC_H */

@@ -335,6 +335,7 @@ void vct_destroy(vct_ctx* c) {
     if (c->spec_rows) (void)hipFree(c->spec_rows);
     bounce_free(c);
     emission_free(c);
+    dynamic_free(c);
     for (auto& s : c->scratch)
         if (s.p) (void)hipFree(s.p);
     for (auto& ss : c->k4s)
@@ -391,8 +392,6 @@ static vct_status voxelize_args(vct_ctx* c, const void* verts, uint32_t stride, 
     if (kd4 && n_mat == 0) return fail(c, VCT_EINVAL, "material_kd4 with n_materials == 0");
     return use_device(c);
 }
-
-static const char* const kKdMessage = "material_kd4: Kd not finite or |Kd| >= 32768";
 
 // K1 on device-resident geometry; `derr` (device int) receives the index-range and Kd flags.
 // dmap (device, may be NULL): each material's diffuse map (vct_voxelize_textured).

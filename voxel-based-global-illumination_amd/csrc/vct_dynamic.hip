@@ -1,0 +1,590 @@
+// vct_dynamic.hip — the dynamic layer (include/vct_dynamic.h; include/vct_spec.h "dynamic
+// layer"): one set of triangles on top of the static grid that is replaced without
+// voxelizing the scene again.
+//
+// K1's state is integer sums accumulated with order-independent atomics, so what a triangle
+// added can be subtracted again exactly (the adds are modulo 2^64, in the packed words too,
+// whatever carried between their halves meanwhile).  An update therefore costs what the old
+// and the new layer cost, not what the scene costs:
+//   k_dyn_setup       one lane per new triangle: k1_tri_setup's arithmetic for a Kd material
+//                     (q, candidate range, the six 16.16 values, the triangle for the G-buffer
+//                     passes behind the static ones), the error word and max|value|.  The
+//                     records are kept in the context: they are the next update's retraction.
+//   k_dyn_scan        the exclusive scan of the candidate counts, one block (a large layer
+//                     takes K1's three scan kernels, vct_voxel_sat.h).
+//   k_dyn_candidates  one lane per 2 (triangle, voxel) candidates, grid-stride over the flat
+//                     list (the total stays on the device: nothing is read back before the
+//                     launch): the SAT, then the hit's values times `sign` into the record in
+//                     the layout the grid has (4 or 7 atomics, none returning).  The old
+//                     layer's records run with sign -1, the new layer's with +1; the +1 pass
+//                     also sets the voxel's bit in the layer's bit mask (no first-hit logic:
+//                     with both signs in flight a count of 0 proves nothing).
+//   k_dyn_list        the voxels of old mask | new mask as a list (k2_list's scheme), and the
+//                     number of voxels the new layer hit.
+//   k_dyn_fixup       one lane per listed voxel: count 0 -> vacate (occupancy bit, albedo,
+//                     normal and level-0 texel to zero; the record is all zero already), else
+//                     set the bit and resolve with resolve_voxel.  A packed record whose
+//                     count x max|value| (the larger of the static pass's and the layer's)
+//                     could reach 2^31 raises the redo flag instead.
+//   k_dyn_occ_list    the occupied list for the new occupancy; then K3's live blocks.
+// One wait for the stream, at the end: error word, redo flag, counts.  Redo (rare; the result
+// is the same either way): retract the new layer again, k_dyn_unpack the occupied records in
+// place into the seven-atomic layout, add it unpacked and fix the listed voxels up again.
+// Nothing here is proportional to n^3 x record size or to the static triangle count: the
+// grid-sized passes are over bit words (n^3 / 8 bytes each).
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include "vct_internal.h"
+#include "vct_voxel_sat.h"
+
+namespace vct {
+namespace {
+
+constexpr int kSlotTmp = 1, kSlotList = 4;   // vct_ctx::scratch: K1's temps, K2's work list (same sizes)
+constexpr uint32_t kAddBlocks = 1024;        // blocks of the +1 pass (its total is not known on the host)
+// Candidates per lane.  K1 takes 8 (kCandPerThread) to amortise its triangle search over a
+// scene's millions of candidates; a layer has tens of thousands, which at 8 per lane fill a
+// few dozen waves that each walk a chain of dependent loads: the pass is latency-bound, so
+// fewer candidates per lane and more waves (tools/dynamic_bench.py)
+constexpr int kDynCandPerThread = 2;
+constexpr uint32_t kSmallScan = 64 * kScanTile;   // triangles up to which one block scans the counts
+
+struct DynFix {       // 48 B
+    long long fix[6]; // albedo rgb, face normal xyz in 16.16 fixed point
+};
+
+struct DynHead {      // per layer, on the device; read back once per update
+    unsigned long long total;   // candidates
+    uint32_t maxabs;            // largest |value| a hit adds, clamped at 2^31
+    int err;                    // kK1ErrIndex | kK1ErrKd
+    int redo;                   // kK1ErrRedo: a packed record may have overflowed
+    uint32_t n_touched;         // entries of the fix-up list
+    uint32_t n_voxels;          // voxels the layer hit
+    uint32_t pad;
+};
+
+constexpr size_t kRecBytes = sizeof(TriGeom) + sizeof(DynFix) + 8;   // per triangle
+TriGeom* rec_geom(const DynLayer& l) { return (TriGeom*)l.rec; }
+DynFix* rec_fix(const DynLayer& l) { return (DynFix*)((char*)l.rec + sizeof(TriGeom) * l.cap); }
+unsigned long long* rec_offs(const DynLayer& l) {
+    return (unsigned long long*)((char*)l.rec + (sizeof(TriGeom) + sizeof(DynFix)) * l.cap);
+}
+DynHead* rec_head(const DynLayer& l) { return (DynHead*)((char*)l.rec + kRecBytes * l.cap); }
+
+// k1_tri_setup (vct_voxelize.hip) for a Kd material: the same operations in the same order
+__global__ void __launch_bounds__(256) k_dyn_setup(const char* __restrict__ verts, uint32_t stride, uint32_t n_verts,
+                                                   const uint32_t* __restrict__ idx, uint32_t n_tri,
+                                                   const uint32_t* __restrict__ mat, const float4* __restrict__ kd,
+                                                   uint32_t n_mat, int n, float g0x, float g0y, float g0z, float inv_h,
+                                                   TriGeom* __restrict__ geom, DynFix* __restrict__ fixo,
+                                                   unsigned long long* __restrict__ counts,
+                                                   float4* __restrict__ mesh_tri, DynHead* __restrict__ head) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_tri) return;
+    const uint32_t vi[3] = {idx[3 * t], idx[3 * t + 1], idx[3 * t + 2]};
+    const uint32_t m = mat ? mat[t] : 0u;
+    TriGeom g;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) g.q[i] = 0.0f;
+    g.lo[0] = g.lo[1] = g.lo[2] = 0;
+    g.ext[0] = g.ext[1] = g.ext[2] = 0;
+    g.pad = 0;
+    DynFix f;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) f.fix[i] = 0;
+    const float4 z4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (vi[0] >= n_verts || vi[1] >= n_verts || vi[2] >= n_verts || (kd && m >= n_mat)) {
+        atomicOr(&head->err, kK1ErrIndex);
+        geom[t] = g;
+        fixo[t] = f;
+        counts[t] = 0;
+        mesh_tri[4 * t + 0] = z4; mesh_tri[4 * t + 1] = z4; mesh_tri[4 * t + 2] = z4;
+        mesh_tri[4 * t + 3] = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
+        return;
+    }
+    const float4 alb = kd ? kd[m] : make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+    float p[3][3], q[3][3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float* src = (const float*)(verts + (size_t)vi[k] * stride);
+        p[k][0] = src[0]; p[k][1] = src[1]; p[k][2] = src[2];
+        q[k][0] = (p[k][0] - g0x) * inv_h;
+        q[k][1] = (p[k][1] - g0y) * inv_h;
+        q[k][2] = (p[k][2] - g0z) * inv_h;
+    }
+    const bool kd_ok = (fabsf(alb.x) < VCT_KD_LIMIT) & (fabsf(alb.y) < VCT_KD_LIMIT) & (fabsf(alb.z) < VCT_KD_LIMIT);
+    bool finite = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        finite &= (fabsf(q[k][0]) < __builtin_inff()) & (fabsf(q[k][1]) < __builtin_inff()) &
+                  (fabsf(q[k][2]) < __builtin_inff());
+    if (!kd_ok || !finite) {   // the K1 input rule: an error, or a skipped triangle (a zero one for the G-buffer)
+        if (!kd_ok) atomicOr(&head->err, kK1ErrKd);
+        geom[t] = g;
+        fixo[t] = f;
+        counts[t] = 0;
+        mesh_tri[4 * t + 0] = z4; mesh_tri[4 * t + 1] = z4; mesh_tri[4 * t + 2] = z4;
+        mesh_tri[4 * t + 3] = make_float4(alb.x, alb.y, alb.z, __int_as_float(-1));
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { g.q[3 * k] = q[k][0]; g.q[3 * k + 1] = q[k][1]; g.q[3 * k + 2] = q[k][2]; }
+    float e1[3] = {p[1][0] - p[0][0], p[1][1] - p[0][1], p[1][2] - p[0][2]};
+    float e2[3] = {p[2][0] - p[0][0], p[2][1] - p[0][1], p[2][2] - p[0][2]};
+    float fn[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2],
+                   e1[0] * e2[1] - e1[1] * e2[0]};
+    float len = sqrtf(dot3(fn[0], fn[1], fn[2], fn[0], fn[1], fn[2]));
+    if (len > 0.0f) { fn[0] = fn[0] / len; fn[1] = fn[1] / len; fn[2] = fn[2] / len; }
+    else { fn[0] = 0.0f; fn[1] = 0.0f; fn[2] = 0.0f; }
+    f.fix[0] = (long long)roundf(alb.x * VCT_FIXED_ONE);
+    f.fix[1] = (long long)roundf(alb.y * VCT_FIXED_ONE);
+    f.fix[2] = (long long)roundf(alb.z * VCT_FIXED_ONE);
+    f.fix[3] = (long long)roundf(fn[0] * VCT_FIXED_ONE);
+    f.fix[4] = (long long)roundf(fn[1] * VCT_FIXED_ONE);
+    f.fix[5] = (long long)roundf(fn[2] * VCT_FIXED_ONE);
+    {
+        unsigned long long mx = 0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            const unsigned long long a = (unsigned long long)(f.fix[i] < 0 ? -f.fix[i] : f.fix[i]);
+            mx = a > mx ? a : mx;
+        }
+        const uint32_t m32 = mx >= (1ull << 31) ? (1u << 31) : (uint32_t)mx;
+        if (m32 > __hip_atomic_load(&head->maxabs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+            atomicMax(&head->maxabs, m32);
+    }
+    unsigned long long cnt = 1;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        int lo, hi;
+        cand_range(fmin3(q[0][a], q[1][a], q[2][a]), fmax3(q[0][a], q[1][a], q[2][a]), n, lo, hi);
+        g.lo[a] = lo;
+        g.ext[a] = hi >= lo ? (uint32_t)(hi - lo + 1) : 0u;
+        cnt *= g.ext[a];
+    }
+    geom[t] = g;
+    fixo[t] = f;
+    counts[t] = cnt;
+    mesh_tri[4 * t + 0] = make_float4(p[0][0], p[0][1], p[0][2], 0.0f);
+    mesh_tri[4 * t + 1] = make_float4(e1[0], e1[1], e1[2], 0.0f);
+    mesh_tri[4 * t + 2] = make_float4(e2[0], e2[1], e2[2], 0.0f);
+    mesh_tri[4 * t + 3] = make_float4(alb.x, alb.y, alb.z, __int_as_float(-1));
+}
+
+// the exclusive scan of a layer's candidate counts in one block (k_scan_carry's loop over the
+// counts themselves): one launch instead of three for the few thousand triangles of a layer
+__global__ void __launch_bounds__(kScanBlock) k_dyn_scan(const unsigned long long* __restrict__ in,
+                                                         unsigned long long* __restrict__ out, uint32_t count,
+                                                         unsigned long long* __restrict__ total_out) {
+    __shared__ unsigned long long sh[4];
+    unsigned long long carry = 0;
+    for (uint32_t b = 0; b < count; b += kScanTile) {
+        const uint32_t base = b + threadIdx.x * kScanItems;
+        unsigned long long v[kScanItems], s = 0, tot;
+#pragma unroll
+        for (int i = 0; i < kScanItems; ++i) {
+            v[i] = base + i < count ? in[base + i] : 0ull;
+            s += v[i];
+        }
+        unsigned long long ex = carry + block_excl_scan(s, sh, tot);
+#pragma unroll
+        for (int i = 0; i < kScanItems; ++i) {
+            if (base + i < count) out[base + i] = ex;
+            ex += v[i];
+        }
+        carry += tot;
+    }
+    if (threadIdx.x == 0) *total_out = carry;
+}
+
+// One lane = kDynCandPerThread consecutive candidates per sweep of the flat list.  NEG: the
+// values are subtracted (two's complement: the modular inverse of what the +1 pass added).
+// layer_bits (the +1 pass): the hit voxel's bit.  Every index is bounded: t < n_tri by the
+// search over offs[0 .. n_tri), the voxel by cand_range's clamp to [0, n - 1].
+template <bool PACKED, bool NEG>
+__global__ void __launch_bounds__(256) k_dyn_candidates(const TriGeom* __restrict__ geom, const DynFix* __restrict__ fixr,
+                                                        const unsigned long long* __restrict__ offs, uint32_t n_tri,
+                                                        const DynHead* __restrict__ head, int n,
+                                                        long long* __restrict__ accum,
+                                                        unsigned long long* __restrict__ layer_bits) {
+    const unsigned long long total = head->total;
+    const unsigned long long sweep = (unsigned long long)gridDim.x * blockDim.x * kDynCandPerThread;
+    for (unsigned long long c0 = ((unsigned long long)blockIdx.x * blockDim.x + threadIdx.x) * kDynCandPerThread; c0 < total;
+         c0 += sweep) {
+        // the last triangle whose first candidate is <= c0 (zero-count triangles share their
+        // successor's offset, so the search lands past them); a layer is a few thousand
+        // triangles: a dozen steps
+        uint32_t lo = 0, hi = n_tri;
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (offs[mid] <= c0) lo = mid; else hi = mid;
+        }
+        uint32_t t = lo;
+        unsigned long long next = t + 1 < n_tri ? offs[t + 1] : total;
+        for (int k = 0; k < kDynCandPerThread; ++k) {
+            const unsigned long long c = c0 + k;
+            if (c >= total) break;
+            while (c >= next) { ++t; next = t + 1 < n_tri ? offs[t + 1] : total; }
+            const TriGeom& g = geom[t];
+            const unsigned long long local = c - offs[t];
+            const uint32_t ex = g.ext[0], ey = g.ext[1];
+            const uint32_t x = (uint32_t)(local % ex);
+            const unsigned long long r = local / ex;
+            const uint32_t y = (uint32_t)(r % ey);
+            const uint32_t z = (uint32_t)(r / ey);
+            const int vx = g.lo[0] + (int)x, vy = g.lo[1] + (int)y, vz = g.lo[2] + (int)z;
+            float q[9];
+#pragma unroll
+            for (int i = 0; i < 9; ++i) q[i] = g.q[i];
+            if (!tri_box_overlap(q, (float)vx + 0.5f, (float)vy + 0.5f, (float)vz + 0.5f)) continue;
+            const size_t v = (size_t)vx + (size_t)n * ((size_t)vy + (size_t)n * (size_t)vz);
+            unsigned long long* a = (unsigned long long*)(accum + 8 * v);
+            const DynFix& f = fixr[t];
+            if constexpr (PACKED) {
+                const unsigned long long w0 = (unsigned long long)f.fix[0] + ((unsigned long long)f.fix[1] << 32);
+                const unsigned long long w1 = (unsigned long long)f.fix[2] + ((unsigned long long)f.fix[3] << 32);
+                const unsigned long long w2 = (unsigned long long)f.fix[4] + ((unsigned long long)f.fix[5] << 32);
+                atomicAdd(a + 0, NEG ? 0ull - w0 : w0);
+                atomicAdd(a + 1, NEG ? 0ull - w1 : w1);
+                atomicAdd(a + 2, NEG ? 0ull - w2 : w2);
+                atomicAdd(a + 3, NEG ? ~0ull : 1ull);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 6; ++i)
+                    atomicAdd(a + i, NEG ? 0ull - (unsigned long long)f.fix[i] : (unsigned long long)f.fix[i]);
+                atomicAdd(a + 6, NEG ? ~0ull : 1ull);
+            }
+            if (layer_bits) atomicOr(layer_bits + (v >> 6), 1ull << (v & 63));
+        }
+    }
+}
+
+// the fix-up list: the voxels of either layer, in bitmask order; and the new layer's voxel count
+__global__ void __launch_bounds__(256) k_dyn_list(const unsigned long long* __restrict__ old_bits,
+                                                  const unsigned long long* __restrict__ new_bits, size_t nwords,
+                                                  uint32_t* __restrict__ list, DynHead* __restrict__ head,
+                                                  uint32_t* __restrict__ occ_count) {
+    const size_t w = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (w == 0) *occ_count = 0;   // for k_dyn_occ_list, two launches on (saves a 4-byte fill's launch)
+    const unsigned long long nb = w < nwords ? new_bits[w] : 0ull;
+    const unsigned long long ob = w < nwords ? old_bits[w] : 0ull;
+    if (nb) atomicAdd(&head->n_voxels, (uint32_t)__popcll(nb));   // a layer's words are few
+    list_block_words(nb | ob, w, list, &head->n_touched);
+}
+
+template <bool PACKED>
+__global__ void __launch_bounds__(256) k_dyn_fixup(const uint32_t* __restrict__ list, const DynHead* __restrict__ head,
+                                                   const long long* __restrict__ accum,
+                                                   unsigned long long* __restrict__ occ_bits,
+                                                   float4* __restrict__ albedo_occ, float4* __restrict__ normal,
+                                                   float4* __restrict__ level0, uint32_t n, uint32_t static_maxabs,
+                                                   int* __restrict__ redo) {
+    const uint32_t cnt = head->n_touched;
+    const uint32_t maxabs = PACKED ? max(static_maxabs, head->maxabs) : 0u;
+    const float4 z4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < cnt; i += gridDim.x * 256) {
+        const uint32_t v = list[i];
+        const unsigned long long bit = 1ull << (v & 63u);
+        if (accum[8 * (size_t)v + (PACKED ? 3 : 6)] == 0) {   // only the retracted layer was here
+            atomicAnd(occ_bits + (v >> 6), ~bit);
+            albedo_occ[v] = z4;
+            normal[v] = z4;
+            level0[l0_texel(v, n)] = z4;
+        } else {
+            atomicOr(occ_bits + (v >> 6), bit);
+            resolve_voxel<PACKED>(accum, v, albedo_occ, normal, maxabs, redo);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_dyn_occ_list(const unsigned long long* __restrict__ bits, size_t nwords,
+                                                      uint32_t* __restrict__ list, uint32_t* __restrict__ count) {
+    const size_t w = (size_t)blockIdx.x * 256 + threadIdx.x;
+    list_block_words(w < nwords ? bits[w] : 0ull, w, list, count);
+}
+
+// packed records -> the seven-atomic layout, in place: k1_gather's unpack, k1_restore's store
+__global__ void __launch_bounds__(256) k_dyn_unpack(const uint32_t* __restrict__ list, const uint32_t* __restrict__ n_list,
+                                                    long long* __restrict__ accum) {
+    const uint32_t cnt = *n_list;
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < cnt; i += gridDim.x * 256) {
+        longlong2* a = (longlong2*)(accum + 8 * (size_t)list[i]);
+        const longlong2 p0 = a[0], p1 = a[1];
+        long long s[6];
+        unpack_sums(p0.x, s[0], s[1]);
+        unpack_sums(p0.y, s[2], s[3]);
+        unpack_sums(p1.x, s[4], s[5]);
+        a[0] = make_longlong2(s[0], s[1]);
+        a[1] = make_longlong2(s[2], s[3]);
+        a[2] = make_longlong2(s[4], s[5]);
+        a[3] = make_longlong2(p1.y, 0);
+    }
+}
+
+vct_status dfail(vct_ctx* c, vct_status s, const std::string& msg) {
+    c->err = msg;
+    return s;
+}
+
+vct_status dhip(vct_ctx* c, hipError_t e, const char* where) {
+    return dfail(c, e == hipErrorOutOfMemory ? VCT_ENOMEM : VCT_EDEVICE,
+                 std::string(where) + ": " + hipGetErrorName(e) + " (" + hipGetErrorString(e) + ")");
+}
+
+#define DYN_HIP(call, where)                                 \
+    do {                                                     \
+        hipError_t e_ = (call);                              \
+        if (e_ != hipSuccess) return dhip(c, e_, where);     \
+    } while (0)
+
+struct DevTmp {   // a staging buffer of the host form, freed on every exit
+    void* p = nullptr;
+    ~DevTmp() { if (p) (void)hipFree(p); }
+};
+
+// `bytes` of *p with the first `keep` bytes preserved (the static scene's triangles)
+vct_status grow_keeping(vct_ctx* c, float4*& p, size_t& cap, size_t bytes, size_t keep) {
+    if (cap >= bytes) return VCT_OK;
+    float4* np = nullptr;
+    DYN_HIP(hipMalloc((void**)&np, bytes), "hipMalloc mesh");
+    hipError_t e = hipSuccess;
+    if (p && keep) e = hipMemcpyAsync(np, p, keep, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // nothing reads the old array any more
+    if (e != hipSuccess) { (void)hipFree(np); return dhip(c, e, "mesh copy"); }
+    if (p) (void)hipFree(p);
+    p = np;
+    cap = bytes;
+    return VCT_OK;
+}
+
+template <bool NEG>
+void launch_candidates(vct_ctx* c, const DynLayer& l, uint32_t n_tri, uint32_t blocks, bool packed,
+                       unsigned long long* layer_bits) {
+    Grid& g = c->grid;
+    if (packed)
+        hipLaunchKernelGGL((k_dyn_candidates<true, NEG>), dim3(blocks), dim3(256), 0, c->stream, rec_geom(l), rec_fix(l),
+                           rec_offs(l), n_tri, rec_head(l), (int)g.n, g.accum, layer_bits);
+    else
+        hipLaunchKernelGGL((k_dyn_candidates<false, NEG>), dim3(blocks), dim3(256), 0, c->stream, rec_geom(l), rec_fix(l),
+                           rec_offs(l), n_tri, rec_head(l), (int)g.n, g.accum, layer_bits);
+}
+
+// blocks that cover `total` candidates in one sweep (more are swept by the kernel's loop)
+uint32_t blocks_for(unsigned long long total) {
+    const unsigned long long b = (total + 256ull * kDynCandPerThread - 1) / (256ull * kDynCandPerThread);
+    return (uint32_t)std::min<unsigned long long>(std::max<unsigned long long>(b, 1), 1u << 20);
+}
+
+void launch_fixup(vct_ctx* c, const uint32_t* list, const DynLayer& nw, bool packed) {
+    Grid& g = c->grid;
+    const size_t nv = (size_t)g.n * g.n * g.n;
+    const uint32_t lb = (uint32_t)std::min<size_t>((nv + 255) / 256, 1024);
+    if (packed)
+        hipLaunchKernelGGL(k_dyn_fixup<true>, dim3(lb), dim3(256), 0, c->stream, list, rec_head(nw), g.accum, g.occ_bits,
+                           g.albedo_occ, g.normal, g.pyr, g.n, g.k1_maxabs, &rec_head(nw)->redo);
+    else
+        hipLaunchKernelGGL(k_dyn_fixup<false>, dim3(lb), dim3(256), 0, c->stream, list, rec_head(nw), g.accum, g.occ_bits,
+                           g.albedo_occ, g.normal, g.pyr, g.n, 0u, &rec_head(nw)->redo);
+}
+
+// Replace the layer with device-resident triangles.  Everything before the first launch
+// leaves the context as it was.
+vct_status dynamic_update(vct_ctx* c, const void* d_verts, uint32_t stride, uint32_t n_verts, const uint32_t* d_idx,
+                          uint32_t n_tri, const uint32_t* d_mat, const float4* d_kd, uint32_t n_mat) {
+    Grid& g = c->grid;
+    Dynamic& d = c->dyn;
+    Mesh& m = c->mesh;
+    hipStream_t s = c->stream;
+    const size_t nv = (size_t)g.n * g.n * g.n, nwords = nv / 64;
+    const bool had = dynamic_live(c);
+    const uint32_t n_static = had ? d.n_static : m.n_tri;
+    if ((uint64_t)n_static + n_tri > 0xffffffffull) return dfail(c, VCT_EINVAL, "voxelize_dynamic: too many triangles");
+    DynLayer& old = d.layer[d.cur];
+    DynLayer& nw = d.layer[1 - d.cur];
+
+    // memory: the two bit masks, the new layer's records, the mesh behind the static triangles
+    if (!d.h_head) DYN_HIP(hipHostMalloc(&d.h_head, sizeof(DynHead), hipHostMallocDefault), "hipHostMalloc");
+    for (DynLayer* l : {&old, &nw})
+        if (!l->bits) {
+            DYN_HIP(hipMalloc((void**)&l->bits, nwords * 8), "hipMalloc layer bits");
+            DYN_HIP(hipMemsetAsync(l->bits, 0, nwords * 8, s), "memset");
+        }
+    if (!nw.rec || nw.cap < n_tri) {
+        DYN_HIP(hipStreamSynchronize(s), "sync");
+        if (nw.rec) (void)hipFree(nw.rec);
+        nw.rec = nullptr;
+        nw.cap = 0;
+        const size_t cap = std::max<size_t>(n_tri, 64);
+        DYN_HIP(hipMalloc(&nw.rec, kRecBytes * cap + sizeof(DynHead)), "hipMalloc layer records");
+        nw.cap = cap;
+    }
+    const size_t all_tri = std::max<size_t>((size_t)n_static + n_tri, 1);
+    vct_status st = grow_keeping(c, m.tri, m.cap, all_tri * 4 * sizeof(float4), (size_t)n_static * 4 * sizeof(float4));
+    if (st != VCT_OK) return st;
+    if (m.textured) {   // the layer's entries exist (its triangles have no diffuse map: never read)
+        st = grow_keeping(c, m.uv, m.uv_cap, all_tri * 2 * sizeof(float4), (size_t)n_static * 2 * sizeof(float4));
+        if (st != VCT_OK) return st;
+        if (n_tri)
+            DYN_HIP(hipMemsetAsync(m.uv + 2 * (size_t)n_static, 0, (size_t)n_tri * 2 * sizeof(float4), s), "memset uv");
+    }
+    const uint32_t n_tiles = (n_tri + kScanTile - 1) / kScanTile;
+    void* tp = nullptr;
+    DYN_HIP(scratch_get(c, kSlotTmp, 8 * (size_t)n_tri + 8 * (size_t)(n_tiles + 1) + 64, &tp), "scratch");
+    unsigned long long* cnt = (unsigned long long*)tp;
+    unsigned long long* tiles = cnt + n_tri;
+    void* lp = nullptr;
+    DYN_HIP(scratch_get(c, kSlotList, 256 + nv * 4, &lp), "scratch");
+    uint32_t* list = (uint32_t*)((char*)lp + 256);
+
+    // what voxelize_dev invalidates; only the success path sets `voxelized` again
+    g.voxelized = g.injected = g.mipped = g.bounced = g.emitted = g.skied = false;
+    g.k2_coarse_ok = g.k3_sparse_ok = g.zm_valid = false;
+    g.k3_live_bz = 0;
+    ++c->grid_epoch;
+    d.live = false;
+    m.n_tri = n_static;
+    if (!had) {   // no layer in place: whatever the record sets hold belongs to an earlier grid
+        old.n_tri = 0;
+        old.total = 0;
+        DYN_HIP(hipMemsetAsync(old.bits, 0, nwords * 8, s), "memset");
+    }
+    DynHead* head = rec_head(nw);
+    DYN_HIP(hipMemsetAsync(nw.bits, 0, nwords * 8, s), "memset");
+    DYN_HIP(hipMemsetAsync(head, 0, sizeof(DynHead), s), "memset");
+    const bool packed = g.accum_packed;
+    if (old.n_tri && old.total) launch_candidates<true>(c, old, old.n_tri, blocks_for(old.total), packed, nullptr);
+    if (n_tri) {
+        hipLaunchKernelGGL(k_dyn_setup, dim3((n_tri + 255) / 256), dim3(256), 0, s, (const char*)d_verts, stride, n_verts,
+                           d_idx, n_tri, d_mat, d_kd, n_mat, (int)g.n, g.g0[0], g.g0[1], g.g0[2], g.inv_h, rec_geom(nw),
+                           rec_fix(nw), cnt, m.tri + 4 * (size_t)n_static, head);
+        if (n_tri <= kSmallScan) {
+            hipLaunchKernelGGL(k_dyn_scan, dim3(1), dim3(kScanBlock), 0, s, cnt, rec_offs(nw), n_tri, &head->total);
+        } else {
+            hipLaunchKernelGGL(k_scan_tiles, dim3(n_tiles), dim3(kScanBlock), 0, s, cnt, rec_offs(nw), tiles, n_tri);
+            hipLaunchKernelGGL(k_scan_carry, dim3(1), dim3(kScanBlock), 0, s, tiles, n_tiles, &head->total);
+            hipLaunchKernelGGL(k_scan_add, dim3(n_tiles), dim3(kScanBlock), 0, s, rec_offs(nw), tiles, n_tri);
+        }
+        launch_candidates<false>(c, nw, n_tri, kAddBlocks, packed, nw.bits);
+    }
+    const uint32_t wb = (uint32_t)((nwords + 255) / 256);
+    hipLaunchKernelGGL(k_dyn_list, dim3(wb), dim3(256), 0, s, old.bits, nw.bits, nwords, list, head, g.occ_count);
+    launch_fixup(c, list, nw, packed);
+    hipLaunchKernelGGL(k_dyn_occ_list, dim3(wb), dim3(256), 0, s, g.occ_bits, nwords, g.occ_list, g.occ_count);
+    DYN_HIP(hipGetLastError(), "voxelize_dynamic");
+    DYN_HIP(launch_k3_live(c), "K3 live blocks");
+    // (into pinned memory: a pageable destination makes the runtime stage the 32 bytes)
+    DYN_HIP(hipMemcpyAsync(d.h_head, head, sizeof(DynHead), hipMemcpyDeviceToHost, s), "read back");
+    DYN_HIP(hipStreamSynchronize(s), "voxelize_dynamic sync");
+    const DynHead h = *(const DynHead*)d.h_head;
+    // a grid from out-of-range indices or an illegal Kd is partial: refused until a vct_voxelize*
+    if (h.err & kK1ErrKd) return dfail(c, VCT_EINVAL, kKdMessage);
+    if (h.err & kK1ErrIndex) return dfail(c, VCT_EINVAL, "voxelize_dynamic: vertex or material index out of range");
+    if ((size_t)h.n_touched > nv || (size_t)h.n_voxels > nv) return dfail(c, VCT_EDEVICE, "voxelize_dynamic: count out of range");
+    if (packed && (h.redo & kK1ErrRedo)) {
+        // the packed records cannot hold the union: take the layer out again (exact, whatever
+        // overflowed meanwhile), unpack what is left, and add the layer in the seven-atomic form
+        if (n_tri && h.total) launch_candidates<true>(c, nw, n_tri, blocks_for(h.total), true, nullptr);
+        const uint32_t lb = (uint32_t)std::min<size_t>((nv + 255) / 256, 4096);
+        hipLaunchKernelGGL(k_dyn_unpack, dim3(lb), dim3(256), 0, s, g.occ_list, g.occ_count, g.accum);
+        g.accum_packed = false;
+        if (n_tri && h.total) launch_candidates<false>(c, nw, n_tri, blocks_for(h.total), false, nullptr);
+        launch_fixup(c, list, nw, false);
+        DYN_HIP(hipGetLastError(), "voxelize_dynamic (unpacked)");
+    }
+    nw.n_tri = n_tri;
+    nw.total = h.total;
+    d.cur = 1 - d.cur;
+    d.live = true;
+    d.epoch = c->grid_epoch;
+    d.n_static = n_static;
+    d.n_voxels = h.n_voxels;
+    m.n_tri = n_static + n_tri;
+    g.voxelized = true;
+    return VCT_OK;
+}
+
+vct_status dynamic_args(vct_ctx* c, const void* verts, uint32_t stride, uint32_t n_idx, const uint32_t* idx,
+                        const float* kd4, uint32_t n_mat) {
+    if (!c->grid.voxelized) return dfail(c, VCT_ESTATE, "voxelize_dynamic without a static grid (voxelize first)");
+    if (n_idx % 3 != 0) return dfail(c, VCT_EINVAL, "voxelize_dynamic: n_idx must be a multiple of 3");
+    if (n_idx > 0 && (!verts || !idx)) return dfail(c, VCT_EINVAL, "voxelize_dynamic: null vertex or index array");
+    if (stride < 12 || stride % 4 != 0)
+        return dfail(c, VCT_EINVAL, "voxelize_dynamic: vertex_stride < 12 or not a multiple of 4");
+    if (kd4 && n_mat == 0) return dfail(c, VCT_EINVAL, "voxelize_dynamic: material_kd4 with n_materials == 0");
+    hipError_t e = hipSetDevice(c->device);
+    if (e != hipSuccess) return dhip(c, e, "hipSetDevice");
+    return VCT_OK;
+}
+
+}  // namespace
+
+void dynamic_free(vct_ctx* c) {
+    for (DynLayer& l : c->dyn.layer) {
+        if (l.rec) (void)hipFree(l.rec);
+        if (l.bits) (void)hipFree(l.bits);
+    }
+    if (c->dyn.h_head) (void)hipHostFree(c->dyn.h_head);
+    c->dyn = Dynamic{};
+}
+
+}  // namespace vct
+
+using namespace vct;
+
+extern "C" vct_status vct_voxelize_dynamic_device(vct_ctx* c, const void* verts, uint32_t stride, uint32_t n_verts,
+                                                  const uint32_t* idx, uint32_t n_idx, const uint32_t* tri_mat,
+                                                  const float* kd4, uint32_t n_mat) {
+    if (!c) return VCT_EINVAL;
+    vct_status st = dynamic_args(c, verts, stride, n_idx, idx, kd4, n_mat);
+    if (st != VCT_OK) return st;
+    if (((uintptr_t)kd4 & 15) || ((uintptr_t)verts & 3) || ((uintptr_t)idx & 3) || ((uintptr_t)tri_mat & 3))
+        return dfail(c, VCT_EINVAL, "voxelize_dynamic: material_kd4 must be 16-byte, verts, idx and tri_material "
+                                    "4-byte aligned");
+    return dynamic_update(c, verts, stride, n_verts, idx, n_idx / 3, tri_mat, (const float4*)kd4, n_mat);
+}
+
+extern "C" vct_status vct_voxelize_dynamic(vct_ctx* c, const void* verts, uint32_t stride, uint32_t n_verts,
+                                           const uint32_t* idx, uint32_t n_idx, const uint32_t* tri_mat,
+                                           const float* kd4, uint32_t n_mat) {
+    if (!c) return VCT_EINVAL;
+    vct_status st = dynamic_args(c, verts, stride, n_idx, idx, kd4, n_mat);
+    if (st != VCT_OK) return st;
+    const uint32_t n_tri = n_idx / 3;
+    // the Kd rule on the host, before any launch: the Kd of every material a triangle uses (an
+    // out-of-range material index is the setup kernel's to report).  Unlike vct_voxelize, which
+    // has nothing to fall back to, the grid and the layer in place stay as they are
+    if (kd4)
+        for (uint32_t t = 0; t < n_tri; ++t) {
+            const uint32_t m = tri_mat ? tri_mat[t] : 0u;
+            if (m >= n_mat) continue;
+            const float* k = kd4 + 4 * (size_t)m;
+            if (!(fabsf(k[0]) < VCT_KD_LIMIT && fabsf(k[1]) < VCT_KD_LIMIT && fabsf(k[2]) < VCT_KD_LIMIT))
+                return dfail(c, VCT_EINVAL, kKdMessage);
+        }
+    DevTmp dv, di, dm, dk;
+    const size_t vbytes = (size_t)stride * n_verts;
+    if (vbytes) DYN_HIP(hipMalloc(&dv.p, vbytes), "hipMalloc verts");
+    if (n_idx) DYN_HIP(hipMalloc(&di.p, (size_t)n_idx * 4), "hipMalloc idx");
+    if (tri_mat && n_tri) DYN_HIP(hipMalloc(&dm.p, (size_t)n_tri * 4), "hipMalloc mat");
+    if (kd4) DYN_HIP(hipMalloc(&dk.p, (size_t)n_mat * 16), "hipMalloc kd");
+    if (vbytes) DYN_HIP(hipMemcpyAsync(dv.p, verts, vbytes, hipMemcpyHostToDevice, c->stream), "upload verts");
+    if (n_idx) DYN_HIP(hipMemcpyAsync(di.p, idx, (size_t)n_idx * 4, hipMemcpyHostToDevice, c->stream), "upload idx");
+    if (dm.p) DYN_HIP(hipMemcpyAsync(dm.p, tri_mat, (size_t)n_tri * 4, hipMemcpyHostToDevice, c->stream), "upload mat");
+    if (dk.p) DYN_HIP(hipMemcpyAsync(dk.p, kd4, (size_t)n_mat * 16, hipMemcpyHostToDevice, c->stream), "upload kd");
+    // (dynamic_update waits for the stream after the last kernel that reads the staging buffers)
+    return dynamic_update(c, dv.p, stride, n_verts, (const uint32_t*)di.p, n_tri, (const uint32_t*)dm.p,
+                          (const float4*)dk.p, n_mat);
+}
+
+// test hook (not part of the headers): 1 / 0 = the grid's records are packed / one sum per word
+extern "C" int vct_debug_accum_packed(const vct_ctx* c) { return c && c->grid.accum_packed ? 1 : 0; }
+
+extern "C" vct_status vct_dynamic_voxels(vct_ctx* c, uint32_t* n_touched) {
+    if (!c || !n_touched) return c ? dfail(c, VCT_EINVAL, "dynamic_voxels: null output") : VCT_EINVAL;
+    if (!c->grid.voxelized) return dfail(c, VCT_ESTATE, "dynamic_voxels before voxelize");
+    *n_touched = dynamic_live(c) ? c->dyn.n_voxels : 0u;
+    return VCT_OK;
+}

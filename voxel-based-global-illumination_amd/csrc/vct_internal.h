@@ -27,6 +27,8 @@ struct Grid {
     // K1 state
     long long* accum = nullptr;      // [n^3][8] int64: albedo rgb, normal xyz, count, pad
     bool accum_packed = false;       // the last K1 packed its sums (r+2^32 g, b+2^32 nx, ny+2^32 nz, count)
+    uint32_t k1_maxabs = 0;          // largest |16.16 value| a hit of the last K1 pass added (clamped at 2^31;
+                                     // 0 after a load): the dynamic layer's packed-sum rule needs the static pass's
     float4* albedo_occ = nullptr;    // [n^3] (albedo rgb, occupancy)
     float4* normal = nullptr;        // [n^3] (unit normal, 0)
     unsigned long long* occ_bits = nullptr;  // [n^3 / 64] occupancy bitmask
@@ -101,6 +103,29 @@ struct Emission {
     bool maybe = false;                   // built, and some triangle had candidates (the count may be > 0)
     uint32_t epoch = 0;                   // vct_ctx::grid_epoch of the build
     int64_t n_host = -1;                  // the count once read back (vct_emission_voxels), -1 unknown
+};
+
+// The dynamic layer (vct_dynamic.hip; vct_spec.h "dynamic layer").  K1's state is integer
+// sums, so a triangle's contribution can be subtracted exactly: the context keeps the
+// current layer's per-triangle setup records (120 bytes each) and the bit mask of the voxels
+// it hit, and an update retracts them and adds the new layer's.  Two record sets, swapped by
+// every update.  The record belongs to the grid of epoch `epoch`: any other voxelization or
+// load bumps vct_ctx::grid_epoch and thereby drops it (the grid it leaves is the static one).
+struct DynLayer {
+    void* rec = nullptr;                  // geom | fix | offsets of `cap` triangles, then the head (device)
+    size_t cap = 0;                       // triangles `rec` holds
+    uint32_t n_tri = 0;
+    unsigned long long total = 0;         // candidates (host copy of the head's)
+    unsigned long long* bits = nullptr;   // [n^3 / 64] voxels the layer hit
+};
+struct Dynamic {
+    DynLayer layer[2];
+    int cur = 0;                          // the layer in place; 1 - cur is built by the next update
+    bool live = false;                    // a record exists ...
+    uint32_t epoch = 0;                   // ... for the grid of this vct_ctx::grid_epoch
+    uint32_t n_static = 0;                // triangles of Mesh::tri that are the static scene's
+    uint32_t n_voxels = 0;                // voxels the layer in place hits (vct_dynamic_voxels)
+    void* h_head = nullptr;               // pinned host copy of an update's read-back (counts, error word)
 };
 
 struct Mesh {
@@ -257,7 +282,8 @@ struct vct_ctx {
                                   // 2-3 G-buffer bins, 4 K2 work list, 7 K1 candidate bucket table,
                                   // 8 multi-device tiles / gather, 9 multi-device step counters,
                                   // 10 shadow-cone step tables, 11 occupancy ranks of the emission build,
-                                  // which also reuses 1 and 7 as K1 does)
+                                  // which also reuses 1 and 7 as K1 does; the dynamic layer's update
+                                  // reuses 1 for its scan temps and 4 for its fix-up list)
     float shadow_tau[VCT_MAX_LIGHTS] = {};   // the apertures whose step tables scratch 10 holds, slot by slot
     uint32_t shadow_taus = 0;                // (vct_shadow.hip; 0: none built yet)
     // The tables are shared by every vct_shadow_cones_device call whatever stream the caller
@@ -276,6 +302,7 @@ struct vct_ctx {
     vct::K4Tuner k4tune;                // timed-form choice of the default cone trace
     vct::Bounce bounce;                 // source list of vct_inject_bounces
     vct::Emission em;                   // emission grid of vct_voxelize_emission*
+    vct::Dynamic dyn;                   // dynamic layer of vct_voxelize_dynamic*
     uint32_t grid_epoch = 0;            // bumped by every voxelization (a new scene for the tuner)
     vct::StepRow* step_tab = nullptr;   // [kMaxStepRows] diffuse-cone step table (device)
     unsigned* spec_keys = nullptr;      // [2 * kSpecSlots]: specular table keys (~0u free), then states
@@ -326,6 +353,8 @@ inline const char* check_color(const float* color) {
 // kK1ErrRedo (packed sums may have overflowed: repeat with packed = false); nothing is
 // read back here, so the launch queues without a synchronisation after the candidate count.
 constexpr int kK1ErrIndex = 1, kK1ErrRedo = 2, kK1ErrKd = 4;
+// the text of a Kd that breaks the K1 input rule, from the host check or the device flag
+constexpr const char* kKdMessage = "material_kd4: Kd not finite or |Kd| >= 32768";
 hipError_t launch_voxelize(vct_ctx* c, const void* d_verts,
                            uint32_t stride, uint32_t n_verts, const uint32_t* d_idx, uint32_t n_tri,
                            const uint32_t* d_mat, const float4* d_kd, uint32_t n_mat, const int32_t* d_map,
@@ -367,6 +396,10 @@ inline bool emission_live(const vct_ctx* c) {
     return c->em.built && c->em.epoch == c->grid_epoch && c->em.maybe && c->em.n_host != 0;
 }
 void emission_free(vct_ctx* c);
+// dynamic layer (vct_dynamic.hip): the context holds a layer record for the current grid;
+// release with the context
+inline bool dynamic_live(const vct_ctx* c) { return c->dyn.live && c->dyn.epoch == c->grid_epoch; }
+void dynamic_free(vct_ctx* c);
 // ray reordering (variant 0x8000, vct_reorder.hip): *perm = the frame's pixels sorted by the
 // Morton code of their cone origin's voxel, background last (device, w * h entries)
 // (perm_spec, nullable: a second order for the specular part, by cell and cone aperture)

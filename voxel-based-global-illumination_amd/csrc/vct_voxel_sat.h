@@ -1,12 +1,14 @@
 // vct_voxel_sat.h — what the translation units that run K1's conservative voxelization
-// pass share (vct_voxelize.hip: K1; vct_emission.hip: the emission grid): the per-triangle
-// candidate record and range, the exclusive scan of the candidate counts, the 32-bit block
-// scan of the list and prefix kernels, the exact 13-axis SAT and the bucket table of the
-// candidates kernel.  Everything is internal to the
+// pass share (vct_voxelize.hip: K1; vct_emission.hip: the emission grid; vct_dynamic.hip: the
+// dynamic layer): the per-triangle candidate record and range, the exclusive scan of the
+// candidate counts, the 32-bit block scan of the list and prefix kernels, the exact 13-axis
+// SAT, the bucket table of the candidates kernel, the list of a bit mask's set bits and the
+// resolve of one accumulator record.  Everything is internal to the
 // including translation unit (vct_spec.h "K1 input rule" has the arithmetic).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "vct_internal.h"
 #include "vct_device.h"
 
 namespace vct {
@@ -157,6 +159,77 @@ __device__ __forceinline__ bool tri_box_overlap(const float* __restrict__ q, flo
         }
     }
     return true;
+}
+
+// ---- the occupied list from a bit mask ------------------------------------------------------
+__device__ __forceinline__ uint32_t lanes_below(unsigned long long m) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+// The set bits of a 256-thread block's words (thread's word `mine` is word w of the mask, 0
+// past its end) appended to `list` in bitmask order: per word, lane j owns bit j (ballot +
+// mbcnt give coalesced slots), one atomic per block.  Every thread of the block calls it.
+__device__ __forceinline__ void list_block_words(unsigned long long mine, size_t w, uint32_t* __restrict__ list,
+                                                 uint32_t* __restrict__ count) {
+    __shared__ uint32_t s_base;
+    const uint32_t lane = threadIdx.x & 63;
+    uint32_t total;
+    const uint32_t excl = block_excl_scan((uint32_t)__popcll(mine), total);
+    if (total == 0) return;                                  // block-uniform
+    if (threadIdx.x == 0) s_base = atomicAdd(count, total);
+    __syncthreads();
+    const uint32_t base = s_base;
+    const size_t w0 = w - lane;                              // the wave's first word
+    for (int i = 0; i < 64; ++i) {
+        const unsigned long long m =
+            ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(mine >> 32), i) << 32) |
+            (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)mine, i);
+        if (m == 0ull) continue;
+        const uint32_t start = base + (uint32_t)__builtin_amdgcn_readlane((int)excl, i);
+        if ((m >> lane) & 1ull) list[start + lanes_below(m)] = (uint32_t)((w0 + i) * 64 + lane);
+    }
+}
+
+// ---- K1's accumulator record -> the resolved voxel -------------------------------------------
+// a packed word's two sums (|sum| < 2^31 each)
+__host__ __device__ __forceinline__ void unpack_sums(long long w, long long& lo, long long& hi) {
+    lo = (long long)(int32_t)(uint32_t)(unsigned long long)w;
+    hi = (long long)(((unsigned long long)w - (unsigned long long)lo)) >> 32;
+}
+
+// PACKED: a voxel whose count x maxabs could reach 2^31 ORs kK1ErrRedo into *overflow and is
+// left as it was (its packed sums cannot be trusted)
+template <bool PACKED>
+__device__ __forceinline__ void resolve_voxel(const long long* __restrict__ accum, size_t v,
+                                              float4* __restrict__ albedo_occ, float4* __restrict__ normal,
+                                              uint32_t maxabs, int* __restrict__ overflow) {
+    long long s[7];
+    {
+        const longlong2* a = (const longlong2*)(accum + 8 * v);
+        longlong2 p0 = a[0], p1 = a[1], p2 = a[2], p3 = a[3];
+        if constexpr (PACKED) {
+            s[6] = p1.y;
+            if ((unsigned long long)s[6] * maxabs >= (1ull << 31)) {
+                atomicOr(overflow, kK1ErrRedo);
+                return;
+            }
+            unpack_sums(p0.x, s[0], s[1]);
+            unpack_sums(p0.y, s[2], s[3]);
+            unpack_sums(p1.x, s[4], s[5]);
+        } else {
+            s[0] = p0.x; s[1] = p0.y; s[2] = p1.x; s[3] = p1.y; s[4] = p2.x; s[5] = p2.y; s[6] = p3.x;
+        }
+    }
+    const unsigned long long cnt = (unsigned long long)s[6];
+    double den = (double)cnt * VCT_FIXED_ONE_D;
+    float4 ao = make_float4((float)((double)s[0] / den), (float)((double)s[1] / den),
+                            (float)((double)s[2] / den), 1.0f);
+    double sx = (double)s[3], sy = (double)s[4], sz = (double)s[5];
+    double len = sqrt((sx * sx + sy * sy) + sz * sz);
+    float4 nm = len > 0.0 ? make_float4((float)(sx / len), (float)(sy / len), (float)(sz / len), 0.0f)
+                          : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    albedo_occ[v] = ao;
+    normal[v] = nm;
 }
 
 constexpr int kCandPerThread = 8;

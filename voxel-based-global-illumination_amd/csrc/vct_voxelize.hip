@@ -266,21 +266,11 @@ __global__ void __launch_bounds__(256) k1_clear(const uint32_t* __restrict__ lis
     }
 }
 
-// a packed word's two sums (|sum| < 2^31 each)
-__host__ __device__ __forceinline__ void unpack_sums(long long w, long long& lo, long long& hi) {
-    lo = (long long)(int32_t)(uint32_t)(unsigned long long)w;
-    hi = (long long)(((unsigned long long)w - (unsigned long long)lo)) >> 32;
-}
-
 // K1 resolve: accumulators -> albedo/occupancy, normal of the voxels K1 hit (the
 // occupied list k2_list builds from their bits; the other voxels stay zero).  PACKED: a
 // voxel whose count x max|value| could reach 2^31 ORs kK1ErrRedo into *overflow (the pass's
-// error word) instead; the host then repeats the voxelization unpacked
-template <bool PACKED>
-__device__ __forceinline__ void resolve_voxel(const long long* __restrict__ accum, size_t v,
-                                              float4* __restrict__ albedo_occ, float4* __restrict__ normal,
-                                              uint32_t maxabs, int* __restrict__ overflow);
-
+// error word) instead; the host then repeats the voxelization unpacked (resolve_voxel:
+// vct_voxel_sat.h)
 template <bool PACKED>
 __global__ void __launch_bounds__(256) k1_resolve(const long long* __restrict__ accum,
                                                   const uint32_t* __restrict__ list, const uint32_t* __restrict__ n_list,
@@ -290,39 +280,6 @@ __global__ void __launch_bounds__(256) k1_resolve(const long long* __restrict__ 
     const uint32_t maxabs = PACKED ? *maxabs_p : 0u;
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < cnt; i += gridDim.x * 256)
         resolve_voxel<PACKED>(accum, list[i], albedo_occ, normal, maxabs, overflow);
-}
-
-template <bool PACKED>
-__device__ __forceinline__ void resolve_voxel(const long long* __restrict__ accum, size_t v,
-                                              float4* __restrict__ albedo_occ, float4* __restrict__ normal,
-                                              uint32_t maxabs, int* __restrict__ overflow) {
-    long long s[7];
-    {
-        const longlong2* a = (const longlong2*)(accum + 8 * v);
-        longlong2 p0 = a[0], p1 = a[1], p2 = a[2], p3 = a[3];
-        if constexpr (PACKED) {
-            s[6] = p1.y;
-            if ((unsigned long long)s[6] * maxabs >= (1ull << 31)) {
-                atomicOr(overflow, kK1ErrRedo);
-                return;
-            }
-            unpack_sums(p0.x, s[0], s[1]);
-            unpack_sums(p0.y, s[2], s[3]);
-            unpack_sums(p1.x, s[4], s[5]);
-        } else {
-            s[0] = p0.x; s[1] = p0.y; s[2] = p1.x; s[3] = p1.y; s[4] = p2.x; s[5] = p2.y; s[6] = p3.x;
-        }
-    }
-    const unsigned long long cnt = (unsigned long long)s[6];
-    double den = (double)cnt * VCT_FIXED_ONE_D;
-    float4 ao = make_float4((float)((double)s[0] / den), (float)((double)s[1] / den),
-                            (float)((double)s[2] / den), 1.0f);
-    double sx = (double)s[3], sy = (double)s[4], sz = (double)s[5];
-    double len = sqrt((sx * sx + sy * sy) + sz * sz);
-    float4 nm = len > 0.0 ? make_float4((float)(sx / len), (float)(sy / len), (float)(sz / len), 0.0f)
-                          : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    albedo_occ[v] = ao;
-    normal[v] = nm;
 }
 
 // ---- K2 injection ----------------------------------------------------------
@@ -338,32 +295,12 @@ __device__ __forceinline__ void resolve_voxel(const long long* __restrict__ accu
 //              (same cells, same float sequence, same result).
 // Level 0 is zeroed first; every voxel's value depends on that voxel alone, so
 // the list order (waves append in any order) does not change the output.
-__device__ __forceinline__ uint32_t lanes_below(unsigned long long m) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
-// one block = 256 words; entries in bitmask order; one atomic per block
+// one block = 256 words; entries in bitmask order; one atomic per block (list_block_words:
+// vct_voxel_sat.h)
 __global__ void __launch_bounds__(256) k2_list(const unsigned long long* __restrict__ bits, size_t nwords,
                                                uint32_t* __restrict__ list, uint32_t* __restrict__ count) {
-    __shared__ uint32_t s_base;
     const size_t w = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const uint32_t lane = threadIdx.x & 63;
-    const unsigned long long mine = w < nwords ? bits[w] : 0ull;
-    uint32_t total;
-    const uint32_t excl = block_excl_scan((uint32_t)__popcll(mine), total);
-    if (total == 0) return;                                  // block-uniform
-    if (threadIdx.x == 0) s_base = atomicAdd(count, total);
-    __syncthreads();
-    const uint32_t base = s_base;
-    const size_t w0 = w - lane;                              // the wave's first word
-    for (int i = 0; i < 64; ++i) {
-        const unsigned long long m =
-            ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(mine >> 32), i) << 32) |
-            (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)mine, i);
-        if (m == 0ull) continue;
-        const uint32_t start = base + (uint32_t)__builtin_amdgcn_readlane((int)excl, i);
-        if ((m >> lane) & 1ull) list[start + lanes_below(m)] = (uint32_t)((w0 + i) * 64 + lane);
-    }
+    list_block_words(w < nwords ? bits[w] : 0ull, w, list, count);
 }
 
 // one block = a chunk of 16 x 256 occupied entries: unlit voxels get (0,0,0,1)
@@ -630,6 +567,7 @@ hipError_t voxelize_pass(vct_ctx* c, const void* d_verts, uint32_t stride, uint3
     if ((e = hipMemsetAsync(g.occ_count, 0, 4, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(total, 0, 16, s)) != hipSuccess) return e;   // total, max|value|
     bool use_packed = false;
+    g.k1_maxabs = 0;
     if (n_tri > 0) {
         hipLaunchKernelGGL(k1_tri_setup, dim3((n_tri + 255) / 256), dim3(256), 0, s,
                            (const char*)d_verts, stride, n_verts, d_idx, n_tri, d_mat, d_kd, n_mat, d_map,
@@ -646,6 +584,7 @@ hipError_t voxelize_pass(vct_ctx* c, const void* d_verts, uint32_t stride, uint3
         if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
         const unsigned long long h_total = h_head[0];
         const uint32_t h_maxabs = (uint32_t)h_head[1];
+        g.k1_maxabs = h_maxabs;   // kept for the dynamic layer's packed-sum rule (vct_dynamic.hip)
         // a voxel's count never exceeds n_tri: with n_tri x max|value| < 2^31 the resolve's
         // overflow check can never fire; otherwise it may (then the caller repeats the pass
         // unpacked).  When a handful of hits could already overflow: unpacked outright
@@ -762,6 +701,7 @@ hipError_t launch_k1_restore(vct_ctx* c, const uint32_t* d_idx, uint32_t cnt, co
     hipLaunchKernelGGL(k2_list, dim3((uint32_t)((nwords + 255) / 256)), dim3(256), 0, s, g.occ_bits, nwords,
                        g.occ_list, g.occ_count);
     g.accum_packed = false;
+    g.k1_maxabs = 0;
     hipLaunchKernelGGL(k1_resolve<false>, dim3(lb), dim3(256), 0, s, g.accum, g.occ_list, g.occ_count,
                        g.albedo_occ, g.normal, (const uint32_t*)nullptr, (int*)nullptr);
     return hipGetLastError();

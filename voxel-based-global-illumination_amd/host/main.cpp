@@ -6,6 +6,7 @@
 //   vct_headless <model.obj> [grid=256] [width=800] [height=600] [frames=5] [out.ppm] [devices=1]
 //                [--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32]
 //                [--light SPEC]... [--shadow-tan T] [--sky Z[:H[:G]]]
+//                [--dynamic FILE.obj [--dynamic-offset x,y,z]]
 //   (devices > 1: one process drives that many GPUs through vct_create_multi)
 //   --model: the model matrix of the reference's draw, T(0,-1.75,0) S(0.2)
 //            (r_voxelization.cpp:26-29; default), or none;
@@ -20,6 +21,10 @@
 //   --sky:    a sky (include/vct_sky.h) with up = +y: Z, H and G are the r,g,b of the zenith, the
 //            horizon (default: Z) and the ground (default: 0,0,0).  It is injected per voxel
 //            after the mips and before the bounces, and added per pixel to the diffuse term;
+//   --dynamic: a second model, voxelized as the context's dynamic layer (include/vct_dynamic.h)
+//            on top of the first one's grid; Kd materials only (its diffuse maps are not loaded).
+//            --dynamic-offset: a world-space translation applied after the model matrix of
+//            --model (default 0,0,0).  The grid is fitted to the first model alone;
 //   --light:  one light of a light list (include/vct_lights.h), repeatable, in list order; with
 //            any --light the list replaces the default directional light.  SPEC is colon-
 //            separated fields of comma-separated floats, world units, angles in degrees:
@@ -116,8 +121,23 @@ static bool parse_sky(const std::string& spec, vct_sky* out) {
     return true;
 }
 
+// one --dynamic-offset x,y,z -> out[3]; false: malformed (not exactly three finite numbers)
+static bool parse_offset(const std::string& spec, float out[3]) {
+    const char* p = spec.c_str();
+    for (int j = 0; j < 3; ++j) {
+        char* q = nullptr;
+        out[j] = std::strtof(p, &q);
+        if (q == p || *q != (j < 2 ? ',' : '\0') || !std::isfinite(out[j])) return false;
+        p = q + 1;
+    }
+    return true;
+}
+
 int main(int argc, char** argv) {
     std::vector<std::string> pos;
+    std::string dynamic;
+    bool has_dynamic = false, has_offset = false;
+    float dyn_offset[3] = {0.0f, 0.0f, 0.0f};
     bool ref_model = true, fit_grid = true;
     int bounces = 0;
     std::string linear;
@@ -147,12 +167,23 @@ int main(int argc, char** argv) {
             if (!parse_sky(spec, &sky)) { std::fprintf(stderr, "malformed --sky %s\n", spec.c_str()); return 2; }
             has_sky = true;
         }
+        else if (a == "--dynamic-offset" || a.rfind("--dynamic-offset=", 0) == 0) {
+            const std::string spec = a == "--dynamic-offset" ? (i + 1 < argc ? argv[++i] : "") : a.substr(17);
+            if (!parse_offset(spec, dyn_offset)) { std::fprintf(stderr, "malformed --dynamic-offset %s\n", spec.c_str()); return 2; }
+            has_offset = true;
+        }
+        else if (a == "--dynamic" || a.rfind("--dynamic=", 0) == 0) {
+            dynamic = a == "--dynamic" ? (i + 1 < argc ? argv[++i] : "") : a.substr(10);
+            if (dynamic.empty() || dynamic.rfind("--", 0) == 0) { std::fprintf(stderr, "--dynamic needs a file (--dynamic FILE.obj)\n"); return 2; }
+            has_dynamic = true;
+        }
         else if (a.rfind("--", 0) == 0) { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
         else pos.push_back(a);
     }
     if (pos.empty()) {
         std::fprintf(stderr, "usage: %s model.obj [grid] [width] [height] [frames] [out.ppm] [devices] "
                              "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] [--sky Z[:H[:G]]] "
+                             "[--dynamic FILE.obj [--dynamic-offset x,y,z]] "
                              "[--light dir:d:rgb | point:p:rgb:range | spot:p:d:rgb:range:inner:outer]...\n",
                      argv[0]);
         return 2;
@@ -167,6 +198,7 @@ int main(int argc, char** argv) {
     if (s.grid < 4) { std::fprintf(stderr, "grid must be >= 4\n"); return 2; }
     if (bounces < 0) { std::fprintf(stderr, "--bounces must be >= 0\n"); return 2; }
     if (!(shadow_tan >= 0.0f) || !std::isfinite(shadow_tan)) { std::fprintf(stderr, "--shadow-tan must be finite and >= 0\n"); return 2; }
+    if (has_offset && !has_dynamic) { std::fprintf(stderr, "--dynamic-offset needs --dynamic FILE.obj\n"); return 2; }
     s.bounces = (uint32_t)bounces;
     s.shadow_tan = shadow_tan;
     s.lights = lights;
@@ -197,6 +229,17 @@ int main(int argc, char** argv) {
     std::printf("grid %u: aabb_min %a %a %a extent %a\n", s.grid, (double)s.aabb_min[0], (double)s.aabb_min[1],
                 (double)s.aabb_min[2], (double)s.extent);
     A.models["test"] = model;
+    if (has_dynamic) {   // the dynamic object: the same model matrix, then the world-space offset
+        auto dyn = std::make_shared<Model>();
+        if (!dyn->LoadObj(dynamic, &err, false)) {
+            std::fprintf(stderr, "ERROR::OBJ:: %s\n", err.c_str());
+            return 1;
+        }
+        A.models["dynamic"] = dyn;
+        s.dynamic_model = "dynamic";
+        for (int i = 0; i < 16; ++i) s.dynamic_matrix[i] = s.model[i];
+        for (int k = 0; k < 3; ++k) s.dynamic_matrix[12 + k] = s.model[12 + k] + dyn_offset[k];
+    }
     auto r = std::make_shared<ConeTraceRenderer>("test", s);
     A.renderers["ConeTrace"] = r;
     for (int f = 0; f < frames; ++f) {

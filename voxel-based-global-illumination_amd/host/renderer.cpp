@@ -68,6 +68,36 @@ bool ConeTraceRenderer::rebuild_scene() {
                                      (uint32_t)(kd4.size() / 4), (uint32_t)offsetof(Vertex, TexCoords)),
                "vct_voxelize_textured"))
         return false;
+    scene_dirty_ = false;
+    dynamic_dirty_ = true;              // a voxelization drops the layer: put it back before the light
+    if (!s_.dynamic_model.empty()) return update_dynamic();
+    return relight();
+}
+
+void ConeTraceRenderer::SetDynamicMatrix(const float m[16]) {
+    if (std::memcmp(s_.dynamic_matrix, m, sizeof s_.dynamic_matrix) == 0) return;
+    std::memcpy(s_.dynamic_matrix, m, sizeof s_.dynamic_matrix);
+    dynamic_dirty_ = true;
+}
+
+bool ConeTraceRenderer::update_dynamic() {
+    auto model = AssetsManager::Instance().models[s_.dynamic_model];
+    if (!model) { error_ = "no model '" + s_.dynamic_model + "'"; status_ = VCT_EINVAL; return false; }
+    std::vector<Vertex> v;
+    std::vector<unsigned> idx, tri_mat;
+    std::vector<float> kd4;
+    Model placed = *model;
+    placed.Transform(s_.dynamic_matrix);
+    placed.Flatten(v, idx, tri_mat, kd4);
+    if (!check(vct_voxelize_dynamic(ctx_, v.data(), sizeof(Vertex), (uint32_t)v.size(), idx.data(), (uint32_t)idx.size(),
+                                    tri_mat.data(), kd4.data(), (uint32_t)(kd4.size() / 4)),
+               "vct_voxelize_dynamic"))
+        return false;
+    dynamic_dirty_ = false;
+    return relight();
+}
+
+bool ConeTraceRenderer::relight() {
     if (!s_.lights.empty()) {
         if (!check(vct_inject_lights(ctx_, s_.lights.data(), (uint32_t)s_.lights.size()), "vct_inject_lights"))
             return false;
@@ -77,13 +107,16 @@ bool ConeTraceRenderer::rebuild_scene() {
     if (!check(vct_build_mips(ctx_), "vct_build_mips")) return false;
     if (s_.has_sky && !check(vct_inject_sky(ctx_, &s_.sky), "vct_inject_sky")) return false;
     if (s_.bounces && !check(vct_inject_bounces(ctx_, s_.bounces), "vct_inject_bounces")) return false;
-    scene_dirty_ = false;
     return true;
 }
 
 void ConeTraceRenderer::Render() {
     if (!ctx_ || status_ != VCT_OK) return;
-    if (scene_dirty_ && !rebuild_scene()) return;
+    if (scene_dirty_) {
+        if (!rebuild_scene()) return;
+    } else if (!s_.dynamic_model.empty() && dynamic_dirty_ && !update_dynamic()) {
+        return;
+    }
     auto cam = AssetsManager::Instance().ActiveCamera();
     if (!cam) return;
     const vct_camera vc = cam->ToVct();

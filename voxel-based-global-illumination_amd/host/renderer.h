@@ -6,7 +6,8 @@
 // VoxelizationRenderer::Render (r_voxelization.cpp:4-35) with the C-ABI of
 // include/vct.h: on the first frame (or when the scene/light changes) it runs
 // K1 voxelize -> K2 inject -> K3 mips (-> `bounces` light bounces), and every frame it builds the G-buffer
-// from the active camera and runs K4.  State is pulled from the registry the
+// from the active camera and runs K4.  An optional dynamic model moves without that: when its
+// matrix changed, vct_voxelize_dynamic replaces the layer, then inject -> mips as above.  State is pulled from the registry the
 // way the reference pulls programs/models/camera from its singletons.
 #pragma once
 #include <string>
@@ -50,6 +51,12 @@ struct ConeTraceSettings {
     // model matrix applied to the model's vertices before K1, column-major; main.cpp
     // sets the reference's T(0,-1.75,0) S(0.2) (r_voxelization.cpp:26-29) by default
     float model[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    // a dynamic object (include/vct_dynamic.h): the registry name of a second model (empty:
+    // none) that is voxelized as the context's dynamic layer with its own model matrix.  When
+    // only that matrix changes (SetDynamicMatrix) the frame pays vct_voxelize_dynamic, the
+    // inject and the mips, not K1 over the static scene.  Its materials are Kd only
+    std::string dynamic_model;
+    float dynamic_matrix[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 };
 
 class ConeTraceRenderer : public Renderer {
@@ -59,6 +66,8 @@ public:
     void Render() override;
 
     void MarkSceneDirty() { scene_dirty_ = true; }
+    // move the dynamic object: the next Render() replaces the layer and relights
+    void SetDynamicMatrix(const float m[16]);
     bool ok() const { return status_ == VCT_OK; }
     const std::string& error() const { return error_; }
     double last_trace_ms() const { return last_ms_; }
@@ -71,6 +80,8 @@ public:
 private:
     bool check(vct_status s, const char* what);
     bool rebuild_scene();
+    bool update_dynamic();                // the dynamic model, placed by its matrix, as the context's layer
+    bool relight();                       // inject -> mips (-> sky, bounces), as after every voxelization
     // row f3 into `lin` (float4) or `rgba` (packed 8-bit), with the light list when there is one
     vct_status composite(float* lin, uint32_t* rgba);
 
@@ -84,6 +95,7 @@ private:
     size_t vis_bytes_ = 0;
     void* sky_ = nullptr;                 // (Sk.rgb, vis) plane of the frame's sky call (has_sky), kept
     bool scene_dirty_ = true;
+    bool dynamic_dirty_ = true;           // the dynamic matrix changed since the layer was voxelized
     vct_status status_ = VCT_OK;
     std::string error_;
     double last_ms_ = 0.0;

@@ -598,6 +598,55 @@ class Context:
             raise VctError(_EINVAL, f"inject_sky: expected a VctSky (vct.sky_light), got {type(sky).__name__}")
         self._check(fn(self.h, C.byref(sky)), "inject_sky")
 
+    # -- dynamic layer (include/vct_dynamic.h) --------------------------------
+    def voxelize_dynamic(self, verts: np.ndarray, idx: np.ndarray, tri_material: np.ndarray | None = None,
+                         kd4: np.ndarray | None = None):
+        """vct_voxelize_dynamic: replace the context's dynamic layer with these triangles (Kd
+        materials only); afterwards the grid equals a voxelize of the static mesh followed by
+        them.  An empty idx removes the layer.  Inject and build_mips follow as after voxelize."""
+        fn = _lib.bind_dynamic_extension(self.lib, "vct_voxelize_dynamic")
+        verts = np.ascontiguousarray(verts, dtype=np.float32)
+        if verts.ndim != 2 or verts.shape[1] < 3:
+            raise VctError(_EINVAL, f"voxelize_dynamic: verts must be [V, F >= 3], got {verts.shape}")
+        idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+        mat = None if tri_material is None else np.ascontiguousarray(tri_material, dtype=np.uint32).reshape(-1)
+        kd = None if kd4 is None else np.ascontiguousarray(kd4, dtype=np.float32)
+        if idx.size % 3:
+            raise VctError(_EINVAL, f"voxelize_dynamic: {idx.size} indices, not a multiple of 3")
+        if mat is not None and mat.size != idx.size // 3:
+            raise VctError(_EINVAL, f"voxelize_dynamic: tri_material has {mat.size} entries for "
+                                    f"{idx.size // 3} triangles")
+        if kd is not None and (kd.ndim != 2 or kd.shape[1] != 4):
+            raise VctError(_EINVAL, f"voxelize_dynamic: kd4 must be [materials, 4], got {kd.shape}")
+        self._check(fn(self.h, _fptr(verts), verts.shape[1] * 4, verts.shape[0], _fptr(idx), idx.size,
+                       _fptr(mat) if mat is not None else None, _fptr(kd) if kd is not None else None,
+                       0 if kd is None else kd.shape[0]), "voxelize_dynamic")
+
+    def voxelize_dynamic_device(self, verts, idx, tri_material=None, kd4=None):
+        """vct_voxelize_dynamic_device on torch tensors: verts [V, F >= 3] float32, idx [3T]
+        int32 / uint32, tri_material [T] int32 or None, kd4 [M, 4] float32 or None."""
+        fn = _lib.bind_dynamic_extension(self.lib, "vct_voxelize_dynamic_device")
+        if verts.dim() != 2 or verts.shape[1] < 3:
+            raise VctError(_EINVAL, f"voxelize_dynamic_device: verts must be [V, F >= 3], got {tuple(verts.shape)}")
+        if str(idx.dtype) in _I64:
+            raise VctError(_EINVAL, "voxelize_dynamic_device: idx must be int32 / uint32, not 64-bit")
+        n_idx = idx.numel()
+        if n_idx % 3:
+            raise VctError(_EINVAL, f"voxelize_dynamic_device: {n_idx} indices, not a multiple of 3")
+        if kd4 is not None and (kd4.dim() != 2 or kd4.shape[1] != 4):
+            raise VctError(_EINVAL, f"voxelize_dynamic_device: kd4 must be [materials, 4], got {tuple(kd4.shape)}")
+        nm = 0 if kd4 is None else kd4.shape[0]
+        self._check(fn(self.h, self._dev(verts, "verts"), verts.shape[1] * 4, verts.shape[0],
+                       self._dev(idx, "idx", _I32), n_idx, self._dev(tri_material, "tri_material", _I32, n_idx // 3),
+                       self._dev(kd4, "kd4"), nm), "voxelize_dynamic_device")
+
+    def dynamic_voxels(self) -> int:
+        """vct_dynamic_voxels: voxels the dynamic layer in place hits (0 without one)."""
+        fn = _lib.bind_dynamic_extension(self.lib, "vct_dynamic_voxels")
+        n = C.c_uint32()
+        self._check(fn(self.h, C.byref(n)), "dynamic_voxels")
+        return int(n.value)
+
     # -- grid access ------------------------------------------------------
     def download_level(self, level: int, face: int = 0) -> np.ndarray:
         nl, _ = self.level_dims(level)

@@ -50,6 +50,9 @@ VCT_EMISSION_SCALE_LIMIT = 2.0 ** 111
 # include/vct_sky.h: sky light, likewise HIP only (bind_sky_extension)
 SKY_EXTENSIONS = ("vct_sky_cones_device", "vct_inject_sky")
 
+# include/vct_dynamic.h: the dynamic layer, likewise HIP only (bind_dynamic_extension)
+DYNAMIC_EXTENSIONS = ("vct_voxelize_dynamic", "vct_voxelize_dynamic_device", "vct_dynamic_voxels")
+
 STATUS = {0: "VCT_OK", 1: "VCT_EINVAL", 2: "VCT_ENOMEM", 3: "VCT_EDEVICE", 4: "VCT_ECOMM", 5: "VCT_ESTATE"}
 
 
@@ -315,6 +318,35 @@ def bind_sky_extension(lib: C.CDLL, name: str):
     fn.restype = res
     fn.argtypes = args
     return fn
+
+
+def bind_dynamic_extension(lib: C.CDLL, name: str):
+    """The include/vct_dynamic.h function `name` of `lib`, with its signature declared;
+    AttributeError (naming the library) if this implementation does not export it."""
+    P, u32, i32 = C.c_void_p, C.c_uint32, C.c_int32
+    sig = {
+        "vct_voxelize_dynamic": (i32, [P, P, u32, u32, P, u32, P, P, u32]),
+        "vct_voxelize_dynamic_device": (i32, [P, P, u32, u32, P, u32, P, P, u32]),
+        "vct_dynamic_voxels": (i32, [P, C.POINTER(u32)]),
+    }
+    res, args = sig[name]
+    try:
+        fn = getattr(lib, name)
+    except AttributeError:
+        raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
+                             "(include/vct_dynamic.h is implemented by the HIP library only)") from None
+    fn.restype = res
+    fn.argtypes = args
+    return fn
+
+
+def debug_accum_packed(lib: C.CDLL, handle) -> bool:
+    """Test hook (vct_debug_accum_packed, not part of the headers): K1's records hold two sums
+    per word (the packed layout) rather than one."""
+    fn = lib.vct_debug_accum_packed
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p]
+    return bool(fn(handle))
 
 
 def debug_sky(lib: C.CDLL, handle=None, force64: int = -1, profile: int = -1):
