@@ -430,4 +430,50 @@
  *    emission and sky marks, the emission grid and the bounce source list; vct_inject_*
  *    and vct_build_mips (a full build) follow it as they follow vct_voxelize. */
 
+/* ---- mixed-resolution trace (include/vct_mixed.h; tests/mixed_ref.py restates it) ----
+ *  All arithmetic is float32, one rounding per operation, no fma contraction; integers are
+ *    exact.  K4 is a function of a pixel's G-buffer record (ray order and tile layout change
+ *    no bit), so tracing a frame of copied records gives the copied pixels' own values.
+ *  Cone selection (vct_trace_cones_device): K4 with n_diffuse = 0 for VCT_CONES_SPECULAR, with
+ *    specular = 0 for VCT_CONES_DIFFUSE.  The selected plane and the step and texel counts of
+ *    the selected cones are those of the full launch; a cone set the context lacks gives +0.
+ *  Frames: factor f in {2, 4}; low frame wl = ceil(w / f) by hl = ceil(h / f); low pixel (X, Y)
+ *    covers the full pixels x in [f X, f X + f), y in [f Y, f Y + f), clipped to the frame.
+ *  Pick: candidates are the block's valid pixels (pos.w != 0, K4's rule).  With d = pos - eye,
+ *      key = ((dx dx + dy dy) + dz dz),   a NaN key counts as +Inf;
+ *    the smallest key wins, a tie goes to the lower row-major index y w + x (nearest surface:
+ *    a silhouette belongs to the foreground).  The three records are copied bit for bit,
+ *    lo_src[Y][X] = y w + x.  No candidate: +0 records and lo_src = 0xffffffff.
+ *  Upsample of pixel p = (x, y) with records P, N over any low plane V:
+ *    background (P.w == 0): +0 in all four channels.
+ *    representative (lo_src[y / f][x / f] == y w + x): V[y / f][x / f], all four channels, exactly.
+ *    otherwise four bilinear taps, in integers, in x and likewise in y:
+ *      t = 2 x + 1 - f,  X0 = floor(t / 2f) (X0 may be -1),  r = t - 2f X0,
+ *      tap X0 weighs 2f - r, tap X0 + 1 weighs r;  bw = (x weight) (y weight) <= 64.
+ *    Taps are visited in the order (0,0), (1,0), (0,1), (1,1).  A tap is dropped when it lies
+ *    outside the low frame, bw = 0, or its lo_src = 0xffffffff.  A remaining tap q (records
+ *    Pq, Nq) is accepted when both
+ *      c = (Nx Nqx + Ny Nqy) + Nz Nqz >= normal_cos
+ *      d = |(Nx (Pqx - Px) + Ny (Pqy - Py)) + Nz (Pqz - Pz)| <= plane_eps
+ *    hold; a NaN fails either test.  Per channel the result is S / W: S = bw V of the first
+ *    accepted tap, then S = S + bw V for each further one (bw converted to float, one multiply,
+ *    one add); W = float(integer sum of the accepted bw); one correctly rounded division.
+ *    W = 0: the pixel is a hole.
+ *  Holes: hole k is the k-th hole in row-major pixel order.  k < max_holes: the pixel's three
+ *    records go to entry k of the packed hole G-buffer (64 pixels wide, ceil(max_holes / 64)
+ *    rows; every entry from min(count, max_holes) on is +0), hole_px[k] = y w + x, and the
+ *    plane value is left for the scatter.  k >= max_holes (overflow): the fallback value, the
+ *    same S / W over every remaining tap without the two tests; the pixel's own block always
+ *    supplies one.  count = the number of holes; stats = {representatives, interpolated,
+ *    holes, overflowed} over valid pixels.
+ *  Scatter: plane[hole_px[k]] = hole_plane[k] for k < min(count, max_holes).
+ *  Frame (vct_trace_mixed_device): pick; K4's diffuse cones over the low frame; upsample into
+ *    the diffuse plane; K4's diffuse cones over the hole frame; scatter; K4's specular cone at
+ *    full resolution.  Every representative and every listed hole therefore carries the
+ *    full-resolution trace's diffuse value bit for bit, and the specular plane is the
+ *    full-resolution trace's.  cone_steps = the diffuse steps of the representatives and the
+ *    listed holes plus every specular step.
+ *  Input rule: normal_cos finite in [-1, 1]; plane_eps finite, >= 0, sign bit clear;
+ *    max_holes >= 1 (0 means ceil(w h / 8)); anything else is VCT_EINVAL with nothing written. */
+
 #endif /* VCT_SPEC_H */

@@ -180,7 +180,9 @@ struct Bounce {
 // K4's per-launch scratch, one set per stream: K4 launches on different streams may run
 // concurrently (a host that overlaps consecutive frames), so the cone-split hand-over
 // and the ray-reorder buffers belong to the stream, not to the context.
-enum { kScFlags = 0, kScHand = 1, kScKeys = 2, kScSort = 3, kScOrder = 4, kScN = 5 };
+// (vct_mixed.hip adds three: the plane a cone selection does not ask for, the upsample's hole
+// mask and row counts, and the frame call's low and hole frames)
+enum { kScFlags = 0, kScHand = 1, kScKeys = 2, kScSort = 3, kScOrder = 4, kScUnsel = 5, kScMixUp = 6, kScMixed = 7, kScN = 8 };
 struct StreamScratch {
     hipStream_t s = nullptr;
     bool used = false;
@@ -378,7 +380,10 @@ hipError_t launch_relayout(vct_ctx* c, const float4* src, float4* dst, uint32_t 
 // cfg.specular says, in that compiled form (0 union, 1 occupancy), screen order, without
 // the tuner, the longest-first dispatch or the debug schedule; the tuner's state (and
 // vct_trace_form) is left as it was
-hipError_t launch_trace(vct_ctx* c, const vct_trace_args* a, int bounce_form = -1);
+// cones (vct_mixed.h VCT_CONES_*): the cone sets of the context this launch traces; both of
+// a's plane pointers are written whatever it selects (an unselected plane gets K4's value for
+// no cones)
+hipError_t launch_trace(vct_ctx* c, const vct_trace_args* a, int bounce_form = -1, uint32_t cones = 3u);
 // light bounces (vct_bounce.hip): the source list of the current voxelization (built when
 // c->bounce is stale; synchronises the ctx stream once to read the count back), the copy of
 // level 0 the bounces add to, one gather (K4 over the sources), and level 0 = L0 + A * I

@@ -1759,7 +1759,7 @@ static int k4_form(vct_ctx* c, uint64_t key, const int* cands_in, int n_in, bool
     return f;
 }
 
-hipError_t launch_trace(vct_ctx* c, const vct_trace_args* a, int bounce_form) {
+hipError_t launch_trace(vct_ctx* c, const vct_trace_args* a, int bounce_form, uint32_t cones) {
     const bool bounce = bounce_form >= 0;     // the gather of vct_inject_bounces (vct_internal.h)
     const Grid& g = c->grid;
     TraceK k;
@@ -1786,8 +1786,8 @@ hipError_t launch_trace(vct_ctx* c, const vct_trace_args* a, int bounce_form) {
     k.rank = (int)(a->tile_world ? a->tile_rank : 0);
     k.world = (int)world;
     k.compact = a->tile_compact ? 1 : 0;
-    k.nd = (int)c->cfg.n_diffuse;
-    k.spec_on = (c->cfg.specular && !bounce) ? 1 : 0;
+    k.nd = (cones & VCT_CONES_DIFFUSE) ? (int)c->cfg.n_diffuse : 0;
+    k.spec_on = (c->cfg.specular && !bounce && (cones & VCT_CONES_SPECULAR)) ? 1 : 0;
     k.aniso = g.aniso;
     k.tau_d = c->cfg.n_diffuse == 16 ? VCT_TAN20 : VCT_TAN30;
     k.steps_tab = c->step_tab;
@@ -1850,7 +1850,7 @@ hipError_t launch_trace(vct_ctx* c, const vct_trace_args* a, int bounce_form) {
             // scene or G-buffer under the same key is caught by the drift watch)
             uint64_t key = 1469598103934665603ull;
             for (uint64_t v : {(uint64_t)a->width, (uint64_t)a->height, (uint64_t)k.rank, (uint64_t)k.world,
-                               (uint64_t)k.compact, (uint64_t)c->cfg.n_diffuse, (uint64_t)k.spec_on, (uint64_t)g.n,
+                               (uint64_t)k.compact, (uint64_t)k.nd, (uint64_t)k.spec_on, (uint64_t)g.n,
                                (uint64_t)(a->variant & 0x7ffff00u)})
                 key = (key ^ v) * 1099511628211ull;
             cand = k4_form(c, key, cands, n, !cnt_form, &ev);

@@ -5,7 +5,7 @@
 //
 //   vct_headless <model.obj> [grid=256] [width=800] [height=600] [frames=5] [out.ppm] [devices=1]
 //                [--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32]
-//                [--light SPEC]... [--shadow-tan T] [--sky Z[:H[:G]]]
+//                [--light SPEC]... [--shadow-tan T] [--sky Z[:H[:G]]] [--mixed 2|4]
 //                [--dynamic FILE.obj [--dynamic-offset x,y,z]]
 //   (devices > 1: one process drives that many GPUs through vct_create_multi)
 //   --model: the model matrix of the reference's draw, T(0,-1.75,0) S(0.2)
@@ -21,6 +21,9 @@
 //   --sky:    a sky (include/vct_sky.h) with up = +y: Z, H and G are the r,g,b of the zenith, the
 //            horizon (default: Z) and the ground (default: 0,0,0).  It is injected per voxel
 //            after the mips and before the bounces, and added per pixel to the diffuse term;
+//   --mixed:  2 or 4: the frame is traced at mixed resolution (include/vct_mixed.h): diffuse cones on
+//            a frame that many times smaller per axis, upsampled, holes traced exactly, the
+//            specular cone at full resolution; absent: the full-resolution trace;
 //   --dynamic: a second model, voxelized as the context's dynamic layer (include/vct_dynamic.h)
 //            on top of the first one's grid; Kd materials only (its diffuse maps are not loaded).
 //            --dynamic-offset: a world-space translation applied after the model matrix of
@@ -145,6 +148,7 @@ int main(int argc, char** argv) {
     float shadow_tan = 0.0f;
     bool has_sky = false;
     vct_sky sky{};
+    uint32_t mixed = 0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--model=reference") ref_model = true;
@@ -167,6 +171,11 @@ int main(int argc, char** argv) {
             if (!parse_sky(spec, &sky)) { std::fprintf(stderr, "malformed --sky %s\n", spec.c_str()); return 2; }
             has_sky = true;
         }
+        else if (a == "--mixed" || a.rfind("--mixed=", 0) == 0) {
+            const std::string v = a == "--mixed" ? (i + 1 < argc ? argv[++i] : "") : a.substr(8);
+            if (v != "2" && v != "4") { std::fprintf(stderr, "malformed --mixed %s (2 or 4)\n", v.c_str()); return 2; }
+            mixed = (uint32_t)(v[0] - '0');
+        }
         else if (a == "--dynamic-offset" || a.rfind("--dynamic-offset=", 0) == 0) {
             const std::string spec = a == "--dynamic-offset" ? (i + 1 < argc ? argv[++i] : "") : a.substr(17);
             if (!parse_offset(spec, dyn_offset)) { std::fprintf(stderr, "malformed --dynamic-offset %s\n", spec.c_str()); return 2; }
@@ -182,7 +191,7 @@ int main(int argc, char** argv) {
     }
     if (pos.empty()) {
         std::fprintf(stderr, "usage: %s model.obj [grid] [width] [height] [frames] [out.ppm] [devices] "
-                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] [--sky Z[:H[:G]]] "
+                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] [--sky Z[:H[:G]]] [--mixed 2|4] "
                              "[--dynamic FILE.obj [--dynamic-offset x,y,z]] "
                              "[--light dir:d:rgb | point:p:rgb:range | spot:p:d:rgb:range:inner:outer]...\n",
                      argv[0]);
@@ -204,6 +213,7 @@ int main(int argc, char** argv) {
     s.lights = lights;
     s.has_sky = has_sky;
     s.sky = sky;
+    s.mixed_factor = mixed;
     if (ref_model) ReferenceModelMatrix(s.model);
 
     AssetsManager& A = AssetsManager::Instance();            // assets.cpp:22-45

@@ -136,7 +136,13 @@ void ConeTraceRenderer::Render() {
     a.spec4 = (float*)out_[1];
     a.cone_steps = (unsigned long long*)counter_;
     auto t0 = std::chrono::steady_clock::now();
-    if (!check(vct_trace_device(ctx_, &a), "vct_trace_device")) return;
+    if (s_.mixed_factor) {
+        vct_mixed_params mp{};
+        if (!check(vct_mixed_default_params(ctx_, s_.mixed_factor, &mp), "vct_mixed_default_params")) return;
+        if (!check(vct_trace_mixed_device(ctx_, &a, &mp), "vct_trace_mixed_device")) return;
+    } else if (!check(vct_trace_device(ctx_, &a), "vct_trace_device")) {
+        return;
+    }
     if (!check(vct_synchronize(ctx_), "sync")) return;
     last_ms_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     check(vct_memcpy(ctx_, &last_steps_, counter_, 8, 1), "read counter");

@@ -43,6 +43,10 @@ struct ConeTraceSettings {
     // > 0: the composite's direct term is shadowed by cones of this half-angle tangent toward
     // every light of the frame (include/vct_shadow.h) instead of the hard voxel walk; 0: the walk
     float shadow_tan = 0.0f;
+    // 2 or 4: the frame is traced by vct_trace_mixed_device (include/vct_mixed.h) at that factor
+    // with the header's default parameters -- diffuse cones on the low frame and the holes,
+    // the specular cone at full resolution; 0: vct_trace_device
+    uint32_t mixed_factor = 0;
     // a sky (include/vct_sky.h): injected per voxel after the mips and before the bounces
     // (vct_inject_sky), and added per pixel to the diffuse plane after K4 (vct_sky_cones_device),
     // so every composite shows it through albedo x diffuse

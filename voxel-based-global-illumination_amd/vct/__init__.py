@@ -29,10 +29,11 @@ import numpy as np
 
 from . import _lib
 from ._lib import VCT_ALL_RANKS, VctCamera, VctCommId, VctConfig, VctLight, VctSky, VctTexture, VctTraceArgs
+from ._lib import VCT_CONES_DIFFUSE, VCT_CONES_SPECULAR, VctMixedHoles, VctMixedParams
 
 __all__ = ["Context", "VctError", "VctConfig", "VctCamera", "tiles_for_rank", "tile_offset", "VERTEX_FLOATS",
            "VCT_ALL_RANKS", "comm_frame_layout", "VctLight", "directional_light", "point_light", "spot_light",
-           "VctSky", "sky_light"]
+           "VctSky", "sky_light", "VctMixedParams", "VctMixedHoles", "VCT_CONES_DIFFUSE", "VCT_CONES_SPECULAR"]
 
 VERTEX_FLOATS = 14          # reference Vertex: Position, Normal, TexCoords, Tangent, Bitangent
 VERTEX_STRIDE = VERTEX_FLOATS * 4
@@ -597,6 +598,123 @@ class Context:
         if not isinstance(sky, VctSky):
             raise VctError(_EINVAL, f"inject_sky: expected a VctSky (vct.sky_light), got {type(sky).__name__}")
         self._check(fn(self.h, C.byref(sky)), "inject_sky")
+
+    # -- mixed-resolution trace (include/vct_mixed.h) ------------------------
+    def mixed_params(self, factor, normal_cos=None, plane_eps=None, max_holes=0) -> VctMixedParams:
+        """A vct_mixed_params: the header defaults of this context for `factor`
+        (vct_mixed_default_params), with the fields given replaced."""
+        p = VctMixedParams()
+        fn = _lib.bind_mixed_extension(self.lib, "vct_mixed_default_params")
+        if fn(self.h, factor, C.byref(p)) != 0:      # a factor the header refuses: the calls report it
+            p.normal_cos, p.plane_eps = _lib.VCT_MIXED_NORMAL_COS, 0.0
+            p.factor = factor
+        if normal_cos is not None:
+            p.normal_cos = normal_cos
+        if plane_eps is not None:
+            p.plane_eps = plane_eps
+        p.max_holes = max_holes
+        return p
+
+    @staticmethod
+    def mixed_max_holes(width, height, max_holes=0) -> int:
+        """The hole capacity a frame gets: max_holes, or ceil(width * height / 8) for 0."""
+        return max_holes if max_holes else (width * height + 7) // 8
+
+    def _mixed_args(self, pos4, nrm4, alb4, width, height, eye, diffuse4, spec4, steps_px, cone_steps,
+                    texel_fetches, tile_rank, tile_world, tile_compact, variant):
+        a = VctTraceArgs()
+        px = width * height
+        out_px = tiles_for_rank(width, height, tile_rank, tile_world) * 64 * 64 if tile_compact else px
+        a.pos4 = self._dev(pos4, "pos4", _F32, 4 * px)
+        a.nrm4 = self._dev(nrm4, "nrm4", _F32, 4 * px)
+        a.alb4 = self._dev(alb4, "alb4", _F32, 4 * px)
+        a.width, a.height = width, height
+        a.eye = _f3(eye)
+        a.diffuse4 = self._dev(diffuse4, "diffuse4", _F32, 4 * out_px)
+        a.spec4 = self._dev(spec4, "spec4", _F32, 4 * out_px)
+        a.steps_px = self._dev(steps_px, "steps_px", _I32, px)
+        a.cone_steps = self._dev(cone_steps, "cone_steps", _I64, 1)
+        a.texel_fetches = self._dev(texel_fetches, "texel_fetches", _I64, 1)
+        a.tile_rank, a.tile_world = tile_rank, tile_world
+        a.tile_compact = 1 if tile_compact else 0
+        a.variant = variant
+        return a
+
+    def trace_cones_device(self, cones, pos4, nrm4, alb4, width, height, eye, diffuse4=None, spec4=None,
+                           steps_px=None, cone_steps=None, texel_fetches=None, tile_rank=0, tile_world=1,
+                           tile_compact=False, variant=0):
+        """vct_trace_cones_device: trace_device restricted to `cones` (VCT_CONES_DIFFUSE,
+        VCT_CONES_SPECULAR or both); the plane of an unselected set may be None and is not
+        written."""
+        fn = _lib.bind_mixed_extension(self.lib, "vct_trace_cones_device")
+        a = self._mixed_args(pos4, nrm4, alb4, width, height, eye, diffuse4, spec4, steps_px, cone_steps,
+                             texel_fetches, tile_rank, tile_world, tile_compact, variant)
+        self._check(fn(self.h, C.byref(a), cones), "trace_cones_device")
+
+    def mixed_pick_device(self, pos4, nrm4, alb4, width, height, eye, factor, lo_pos4, lo_nrm4, lo_alb4, lo_src):
+        """vct_mixed_pick_device: the low G-buffer (ceil(width / factor) by ceil(height / factor))
+        and lo_src (int32 / uint32), the full-resolution index of each low pixel's record."""
+        fn = _lib.bind_mixed_extension(self.lib, "vct_mixed_pick_device")
+        n = 4 * width * height
+        f = factor if factor > 0 else 1
+        nl = ((width + f - 1) // f) * ((height + f - 1) // f)
+        self._check(fn(self.h, self._dev(pos4, "pos4", _F32, n), self._dev(nrm4, "nrm4", _F32, n),
+                       self._dev(alb4, "alb4", _F32, n), width, height, C.byref(_f3(eye)), factor,
+                       self._dev(lo_pos4, "lo_pos4", _F32, 4 * nl), self._dev(lo_nrm4, "lo_nrm4", _F32, 4 * nl),
+                       self._dev(lo_alb4, "lo_alb4", _F32, 4 * nl), self._dev(lo_src, "lo_src", _I32, nl)),
+                    "mixed_pick_device")
+
+    def mixed_holes(self, max_holes, pos4, nrm4, alb4, px, count, stats=None) -> VctMixedHoles:
+        """A vct_mixed_holes over device tensors: the packed hole G-buffer (ceil(max_holes / 64)
+        rows of 64 pixels), px (max_holes int32 / uint32), count (1) and stats (4, or None)."""
+        n = 4 * 64 * ((max_holes + 63) // 64)
+        ho = VctMixedHoles()
+        ho.pos4 = self._dev(pos4, "holes.pos4", _F32, n)
+        ho.nrm4 = self._dev(nrm4, "holes.nrm4", _F32, n)
+        ho.alb4 = self._dev(alb4, "holes.alb4", _F32, n)
+        ho.px = self._dev(px, "holes.px", _I32, max_holes)
+        ho.count = self._dev(count, "holes.count", _I32, 1)
+        ho.stats = self._dev(stats, "holes.stats", _I32, 4)
+        ho.max_holes = max_holes
+        return ho
+
+    def mixed_upsample_device(self, pos4, nrm4, alb4, width, height, factor, lo_pos4, lo_nrm4, lo_src, lo_plane4,
+                              params, plane4, holes):
+        """vct_mixed_upsample_device: plane4 from the low plane, and the hole list into `holes`
+        (a VctMixedHoles, Context.mixed_holes)."""
+        fn = _lib.bind_mixed_extension(self.lib, "vct_mixed_upsample_device")
+        if not isinstance(params, VctMixedParams) or not isinstance(holes, VctMixedHoles):
+            raise VctError(_EINVAL, "mixed_upsample: expected a VctMixedParams and a VctMixedHoles")
+        n = 4 * width * height
+        f = factor if factor > 0 else 1
+        nl = ((width + f - 1) // f) * ((height + f - 1) // f)
+        self._check(fn(self.h, self._dev(pos4, "pos4", _F32, n), self._dev(nrm4, "nrm4", _F32, n),
+                       self._dev(alb4, "alb4", _F32, n), width, height, factor,
+                       self._dev(lo_pos4, "lo_pos4", _F32, 4 * nl), self._dev(lo_nrm4, "lo_nrm4", _F32, 4 * nl),
+                       self._dev(lo_src, "lo_src", _I32, nl), self._dev(lo_plane4, "lo_plane4", _F32, 4 * nl),
+                       C.byref(params), self._dev(plane4, "plane4", _F32, n), C.byref(holes)),
+                    "mixed_upsample_device")
+
+    def mixed_scatter_device(self, hole_plane4, holes, plane4):
+        """vct_mixed_scatter_device: plane4[holes.px[k]] = hole_plane4[k] for the listed holes.
+        plane4 must be the frame the list was made for."""
+        fn = _lib.bind_mixed_extension(self.lib, "vct_mixed_scatter_device")
+        if not isinstance(holes, VctMixedHoles):
+            raise VctError(_EINVAL, "mixed_scatter: expected a VctMixedHoles")
+        n = 4 * 64 * ((holes.max_holes + 63) // 64)
+        self._check(fn(self.h, self._dev(hole_plane4, "hole_plane4", _F32, n), C.byref(holes),
+                       self._dev(plane4, "plane4", _F32, 4)), "mixed_scatter_device")
+
+    def trace_mixed_device(self, params, pos4, nrm4, alb4, width, height, eye, diffuse4, spec4, steps_px=None,
+                           cone_steps=None, texel_fetches=None, tile_rank=0, tile_world=1, tile_compact=False,
+                           variant=0):
+        """vct_trace_mixed_device: the mixed-resolution frame (params: Context.mixed_params)."""
+        fn = _lib.bind_mixed_extension(self.lib, "vct_trace_mixed_device")
+        if not isinstance(params, VctMixedParams):
+            raise VctError(_EINVAL, "trace_mixed: expected a VctMixedParams (Context.mixed_params)")
+        a = self._mixed_args(pos4, nrm4, alb4, width, height, eye, diffuse4, spec4, steps_px, cone_steps,
+                             texel_fetches, tile_rank, tile_world, tile_compact, variant)
+        self._check(fn(self.h, C.byref(a), C.byref(params)), "trace_mixed_device")
 
     # -- dynamic layer (include/vct_dynamic.h) --------------------------------
     def voxelize_dynamic(self, verts: np.ndarray, idx: np.ndarray, tri_material: np.ndarray | None = None,

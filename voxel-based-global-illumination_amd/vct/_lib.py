@@ -53,6 +53,14 @@ SKY_EXTENSIONS = ("vct_sky_cones_device", "vct_inject_sky")
 # include/vct_dynamic.h: the dynamic layer, likewise HIP only (bind_dynamic_extension)
 DYNAMIC_EXTENSIONS = ("vct_voxelize_dynamic", "vct_voxelize_dynamic_device", "vct_dynamic_voxels")
 
+# include/vct_mixed.h: the mixed-resolution trace, likewise HIP only (bind_mixed_extension)
+MIXED_EXTENSIONS = ("vct_mixed_default_params", "vct_trace_cones_device", "vct_mixed_pick_device",
+                    "vct_mixed_upsample_device", "vct_mixed_scatter_device", "vct_trace_mixed_device")
+VCT_CONES_DIFFUSE, VCT_CONES_SPECULAR = 1, 2
+VCT_MIXED_NORMAL_COS = 0.9
+VCT_MIXED_HOLE_WIDTH = 64
+VCT_MIXED_NO_SOURCE = 0xFFFFFFFF
+
 STATUS = {0: "VCT_OK", 1: "VCT_EINVAL", 2: "VCT_ENOMEM", 3: "VCT_EDEVICE", 4: "VCT_ECOMM", 5: "VCT_ESTATE"}
 
 
@@ -103,6 +111,27 @@ class VctSky(C.Structure):            # vct_sky, 48 bytes
         ("zenith", C.c_float * 3),
         ("horizon", C.c_float * 3),
         ("ground", C.c_float * 3),
+    ]
+
+
+class VctMixedParams(C.Structure):    # vct_mixed_params, 16 bytes
+    _fields_ = [
+        ("normal_cos", C.c_float),
+        ("plane_eps", C.c_float),
+        ("max_holes", C.c_uint32),
+        ("factor", C.c_uint32),
+    ]
+
+
+class VctMixedHoles(C.Structure):     # vct_mixed_holes
+    _fields_ = [
+        ("pos4", C.c_void_p),
+        ("nrm4", C.c_void_p),
+        ("alb4", C.c_void_p),
+        ("px", C.c_void_p),
+        ("count", C.c_void_p),
+        ("stats", C.c_void_p),
+        ("max_holes", C.c_uint32),
     ]
 
 
@@ -335,6 +364,30 @@ def bind_dynamic_extension(lib: C.CDLL, name: str):
     except AttributeError:
         raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
                              "(include/vct_dynamic.h is implemented by the HIP library only)") from None
+    fn.restype = res
+    fn.argtypes = args
+    return fn
+
+
+def bind_mixed_extension(lib: C.CDLL, name: str):
+    """The include/vct_mixed.h function `name` of `lib`, with its signature declared;
+    AttributeError (naming the library) if this implementation does not export it."""
+    P, u32, i32 = C.c_void_p, C.c_uint32, C.c_int32
+    MP, MH = C.POINTER(VctMixedParams), C.POINTER(VctMixedHoles)
+    sig = {
+        "vct_mixed_default_params": (i32, [P, u32, MP]),
+        "vct_trace_cones_device": (i32, [P, C.POINTER(VctTraceArgs), u32]),
+        "vct_mixed_pick_device": (i32, [P, P, P, P, u32, u32, C.POINTER(C.c_float * 3), u32, P, P, P, P]),
+        "vct_mixed_upsample_device": (i32, [P, P, P, P, u32, u32, u32, P, P, P, P, MP, P, MH]),
+        "vct_mixed_scatter_device": (i32, [P, P, MH, P]),
+        "vct_trace_mixed_device": (i32, [P, C.POINTER(VctTraceArgs), MP]),
+    }
+    res, args = sig[name]
+    try:
+        fn = getattr(lib, name)
+    except AttributeError:
+        raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
+                             "(include/vct_mixed.h is implemented by the HIP library only)") from None
     fn.restype = res
     fn.argtypes = args
     return fn
