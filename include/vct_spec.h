@@ -476,4 +476,79 @@
  *  Input rule: normal_cos finite in [-1, 1]; plane_eps finite, >= 0, sign bit clear;
  *    max_holes >= 1 (0 means ceil(w h / 8)); anything else is VCT_EINVAL with nothing written. */
 
+/* ---- volumetric fog (include/vct_fog.h; tests/fog_ref.py restates it) -------------------
+ *  All arithmetic is float32, one rounding per operation, no contraction; the fused
+ *    operations are the fmaf() written below.  dot3 is "local lights"'.
+ *  Medium: (density, albedo, ambient, level, step), the input rule of vct_fog.h:
+ *    density finite, sign bit clear, <= VCT_FOG_DENSITY_LIMIT; albedo_c finite, in [0, 1], sign
+ *    bit clear; ambient finite and >= 0; 1 <= level and m = n >> level >= 4; 0.25 <= step <= 4.
+ *      sigma_v = (density * E) / (float)n        (multiply, then divide; must be finite)
+ *      cs = 2^level,  ds = step * cs             (both exact)
+ *  Scatter volume (vct_build_fog): cell (i, j, k), 0 <= i, j, k < m, has the centre
+ *      x_c = ((float)i + 0.5f) * cs              (exact), likewise y_c, z_c, in voxel units.
+ *    Per light j in list order, with the per-light host constants of "local lights":
+ *      directional:  l = the light's l, att = 1.0f, t_lim = +inf; never skipped
+ *      point, spot:  d = pL - x_c, r2 = dot3(d, d); skipped unless r2 > 0
+ *                    r = sqrtf(r2), l_c = d_c / r, t_lim = r
+ *                    u = r2 * inv_rr, w = fmaxf(1.0f - u, 0.0f), att = (w * w) / (1.0f + r2 * h2)
+ *      spot only:    cd = dot3(l, a), s = fminf(fmaxf((cd - cos_outer) * inv_span, 0.0f), 1.0f)
+ *                    att = att * (s * s)
+ *      skipped unless att > 0 (out of range, outside the cone).  This is "local lights"' f
+ *      with the receiver q = x_c and without the n.l cosine: a medium has no normal.
+ *      tau = fminf(fmaxf(tan_half[j], VCT_SPEC_TAU_MIN), VCT_SPEC_TAU_MAX)
+ *      a_j = steps 1-5 of "shadow cones" with o = x_c (no normal offset), d = l, tau, t_lim
+ *      V_j = fmaxf(1.0f - a_j / VCT_ALPHA_STOP, 0.0f)
+ *      acc_c = fmaf(C_j,c, att * V_j, acc_c)     from acc = +0 (the product att * V_j rounded first)
+ *    A skipped light marches no cone and leaves acc as it is.
+ *    Ambient (ambient > 0 and n_diffuse > 0): I+ and I- are the rgb of K4's diffuse plane (A.5,
+ *    A.6; the context's diffuse cone set, no specular cone) for the records
+ *      hh = E / (float)n,  P_c = g0_c + x_c,c * hh  (multiply, then add),  P.w = 1,
+ *      normal (0, +1, 0) for I+, (0, -1, 0) for I-
+ *      A_c = 0.5f * (I+_c + I-_c);               A = +0 when n_diffuse = 0
+ *    Cell:  ambient == 0:  S_c = albedo_c * (VCT_FOG_PHASE * acc_c)
+ *           ambient > 0:   S_c = albedo_c * fmaf(ambient, A_c, VCT_FOG_PHASE * acc_c)
+ *           S.w = +0.
+ *  Rays (vct_fog_rays_device): o_c = (eye_c - g0_c) * inv_h, once, on the host.
+ *    valid pixel (pos.w != 0): e_c = (P_c - g0_c) * inv_h, v = e - o,
+ *      len = sqrtf((vx*vx + vy*vy) + vz*vz), d_c = v_c / len       (the K2 direction rule)
+ *    background pixel with a camera: d = the caster's primary-ray direction of the pixel
+ *      (vct_frame.hip pixel_ray: normalised by il = 1.0f / sqrtf(dot3(d, d)), d_c * il), len = +inf
+ *    background pixel without a camera: (+0, +0, +0, +0)
+ *    not a ray -- !(len > 0), a len of a valid pixel that is not finite, or a non-finite
+ *      component of d: (+0, +0, +0, +0).
+ *  March (vct_fog_march_device), per pixel, record (d, len), o as above (must be finite):
+ *    null record: !(len > 0) or a non-finite d_c: result (0, 0, 0, 1), no sample.
+ *    Slab, per axis c, nf = (float)n, inv = 1.0f / d_c:
+ *      d_c == 0 or inv not finite (|d_c| <= 2^-128): the axis does not clip when
+ *        0 <= o_c <= nf holds, and empties the segment otherwise
+ *      else ta = (0.0f - o_c) * inv, tb = (nf - o_c) * inv, tn_c = fminf(ta, tb), tf_c = fmaxf(ta, tb)
+ *      t0 = fmaxf(fmaxf(fmaxf(0.0f, tn_x), tn_y), tn_z)   over the clipping axes
+ *      t1 = fminf(fminf(fminf(len, tf_x), tf_y), tf_z)
+ *      the segment is empty unless t1 > t0.  o and inv are finite and inv != 0, so no t is
+ *      ever NaN (the discipline of the K2 walk's "NaN step" rule).
+ *    Samples: span = t1 - t0, N = (int)fminf(ceilf(span / ds), (float)VCT_FOG_MAX_STEPS)
+ *      sample i < N:  ts = t0 + ((float)i + 0.5f) * ds,  p_c = o_c + d_c * ts  (multiply, add)
+ *      its length:  ds for i < N - 1;  fminf(span - (float)(N - 1) * ds, ds) for i = N - 1
+ *      a_i = fminf(sigma_v * length, 1.0f)
+ *    Trilinear S(p) (A.5's shape, edge clamp instead of zero border): c = p * 2^-level - 0.5f
+ *      (the product exact), fl = floorf(c), w = c - fl, weights (1.0f - w, w) per axis, corner
+ *      indices (int)fl and (int)fl + 1 each clamped to [0, m - 1];
+ *      S_c = fmaf(wc, cell_c, S_c) over the eight corners, x fastest, from +0, wc = (wx * wy) * wz.
+ *    Front to back from F = +0, T = 1, before each sample: end if T < VCT_FOG_T_STOP;
+ *      F_c = fmaf(T * a_i, S_c, F_c);  T = T * (1.0f - a_i);  one sample counted.
+ *    The per-step opacity is linear in the length on purpose: no transcendental enters.
+ *  Apply (vct_fog_apply_device): rgb_c = fmaf(rgb_c, T, F_c), alpha untouched.  The RGBA8
+ *    frame, alpha 255, with tone(v) = (max(v / (1 + v), 0))^VCT_INV_GAMMA and q(v) = the
+ *    composite's rounding to 8 bits: a pixel whose incoming alpha is not 0 gets q(tone(rgb_c)) of
+ *    the new rgb, the composite's own present step.  A pixel with alpha 0 is a background pixel of
+ *    a composite, which presents its clear colour as it is, without the tone curve; the fog goes
+ *    over it in display space, q(fmaf(rgb_c, T, tone(F_c))) with the incoming rgb, so that
+ *    T = 1, F = 0 reproduces the composite's byte.  Without a linear frame the incoming pixel is
+ *    (0, 0, 0, 0): the fog layer alone, q(tone(F_c)). */
+#define VCT_FOG_PHASE          0.0795774715f  /* 1 / (4 pi)                                  */
+#define VCT_FOG_T_STOP         0.00390625f    /* 2^-8                                        */
+#define VCT_FOG_MAX_STEPS      4096           /* > 1024 sqrt(3) / (0.25 * 2): the diagonal of
+                                                 1024^3 at level 1, step 0.25 (3548 samples) */
+#define VCT_FOG_DENSITY_LIMIT  1048576.0f     /* 2^20 per world unit                         */
+
 #endif /* VCT_SPEC_H */

@@ -336,6 +336,7 @@ void vct_destroy(vct_ctx* c) {
     bounce_free(c);
     emission_free(c);
     dynamic_free(c);
+    fog_free(c);
     for (auto& s : c->scratch)
         if (s.p) (void)hipFree(s.p);
     for (auto& ss : c->k4s)

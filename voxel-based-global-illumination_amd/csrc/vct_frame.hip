@@ -6,6 +6,7 @@
 //    follows the reference camera conventions (camera.cpp:24-27,
 //    r_voxelization.cpp:18): vertical FOV = Zoom, aspect w/h, near 0.1, far 100.
 #include "vct_internal.h"
+#include "vct_view.h"
 
 namespace vct {
 namespace {
@@ -88,16 +89,7 @@ __device__ __forceinline__ void ray_tri_bary(float4 v0, float4 e1, float4 e2, fl
     v = dot3(dx, dy, dz, qx, qy, qz) * inv;
 }
 
-// pixel (x, y) -> unit ray direction (row 0 = top; reference camera, r_voxelization.cpp:16-23)
-__device__ __forceinline__ void pixel_ray(const RayK& k, int x, int y, float& dx, float& dy, float& dz) {
-    const float ndx = (2.0f * ((float)x + 0.5f) / (float)k.w - 1.0f) * k.tan_half * k.aspect;
-    const float ndy = (1.0f - 2.0f * ((float)y + 0.5f) / (float)k.h) * k.tan_half;
-    dx = k.fx + ndx * k.rx + ndy * k.ux;
-    dy = k.fy + ndx * k.ry + ndy * k.uy;
-    dz = k.fz + ndx * k.rz + ndy * k.uz;
-    const float il = 1.0f / sqrtf(dot3(dx, dy, dz, dx, dy, dz));
-    dx *= il; dy *= il; dz *= il;
-}
+// pixel_ray (pixel -> unit ray direction) is vct_view.h's, shared with vct_fog.hip
 
 // G-buffer texel of the nearest hit (shared by the brute-force and the binned pass)
 __device__ __forceinline__ void write_gbuffer(const RayK& k, int x, int y, float dx, float dy, float dz, float best,
@@ -302,12 +294,7 @@ struct CompK {
     uint32_t* rgba8;
 };
 
-__device__ __forceinline__ uint32_t to8(float v) {   // Reinhard, gamma 1/2.2, round half away
-    v = v / (1.0f + v);
-    v = powf(v < 0.0f ? 0.0f : v, VCT_INV_GAMMA);
-    const int q = (int)lroundf(v * 255.0f);
-    return (uint32_t)(q < 0 ? 0 : (q > 255 ? 255 : q));
-}
+// the tone curve to8 is vct_view.h's, shared by every composite and the fog apply
 
 __global__ void __launch_bounds__(256) k_composite(CompK k) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -387,13 +374,8 @@ static RayK ray_params(vct_ctx* c, const vct_camera* cam, uint32_t w, uint32_t h
     k.tri = c->mesh.tri; k.n_tri = c->mesh.n_tri;
     k.uv = c->mesh.textured ? c->mesh.uv : nullptr;
     k.texels = c->tex.texels; k.tdesc = c->tex.desc; k.n_tex = c->tex.n;
-    k.w = (int)w; k.h = (int)h;
+    camera_fields(k, cam, w, h);
     k.px = cam->position[0]; k.py = cam->position[1]; k.pz = cam->position[2];
-    k.fx = cam->front[0]; k.fy = cam->front[1]; k.fz = cam->front[2];
-    k.ux = cam->up[0]; k.uy = cam->up[1]; k.uz = cam->up[2];
-    k.rx = cam->right[0]; k.ry = cam->right[1]; k.rz = cam->right[2];
-    k.tan_half = tanf(cam->zoom_deg * 0.5f * 3.14159265358979f / 180.0f);
-    k.aspect = (float)w / (float)h;
     k.near_p = cam->near_plane; k.far_p = cam->far_plane;
     k.rough = rough;
     k.pos = pos; k.nrm = nrm; k.alb = alb;

@@ -81,6 +81,8 @@ struct Grid {
     bool bounced = false;       // vct_inject_bounces has added to this level 0 (cleared with every new level 0)
     bool emitted = false;       // vct_inject_emission has added to this level 0 (cleared where bounced is)
     bool skied = false;         // vct_inject_sky has added to this level 0 (cleared where bounced is)
+    uint64_t mips_serial = 0;   // bumped by every mip build (launch_mips): with `mipped`, the identity of
+                                // the pyramid that vct_build_fog stamps its volume with
 };
 
 // Emissive surfaces (vct_emission.hip; vct_spec.h "emissive surfaces").  The emission grid
@@ -175,6 +177,27 @@ struct Bounce {
     bool profile = false;            // vct_debug_bounce: time the stages with events
     hipEvent_t ev[4] = {};
     float ms[4] = {0, 0, 0, 0};      // list build, gather, accumulate, K3 of the last bounce
+};
+
+// Volumetric fog (vct_fog.hip; vct_spec.h "volumetric fog").  The scatter volume of the last
+// vct_build_fog: m^3 float4 cells in the pyramid's brick layout (vct_device.h texel_index), so
+// a 2x2x2 trilinear footprint lies in one to eight 128-byte bricks.  It belongs to the pyramid
+// of mip build `serial` of voxelization `epoch`: any level-0 change clears Grid::mipped and any
+// mip build bumps Grid::mips_serial, either of which makes it stale.  `gbuf` holds the
+// synthetic G-buffer of the ambient term: position, normal and K4's two outputs for 2 m^3
+// records (normal +y, then -y).
+struct Fog {
+    float4* vol = nullptr;
+    size_t cap = 0;                  // cells `vol` holds
+    uint32_t m = 0, level = 0;
+    bool built = false;
+    uint32_t epoch = 0;
+    uint64_t serial = 0;
+    float4* gbuf = nullptr;
+    size_t gbuf_cap = 0;             // records per plane
+    int path = 0;                    // address path of the last light-cone march: 32 or 64
+    unsigned long long* dbg_light_steps = nullptr;     // vct_debug_fog (tools): device counters the builds
+    unsigned long long* dbg_ambient_steps = nullptr;   // add their light-cone / ambient K4 steps to
 };
 
 // K4's per-launch scratch, one set per stream: K4 launches on different streams may run
@@ -305,6 +328,7 @@ struct vct_ctx {
     vct::Bounce bounce;                 // source list of vct_inject_bounces
     vct::Emission em;                   // emission grid of vct_voxelize_emission*
     vct::Dynamic dyn;                   // dynamic layer of vct_voxelize_dynamic*
+    vct::Fog fog;                       // scatter volume of vct_build_fog
     uint32_t grid_epoch = 0;            // bumped by every voxelization (a new scene for the tuner)
     vct::StepRow* step_tab = nullptr;   // [kMaxStepRows] diffuse-cone step table (device)
     unsigned* spec_keys = nullptr;      // [2 * kSpecSlots]: specular table keys (~0u free), then states
@@ -405,6 +429,13 @@ void emission_free(vct_ctx* c);
 // release with the context
 inline bool dynamic_live(const vct_ctx* c) { return c->dyn.live && c->dyn.epoch == c->grid_epoch; }
 void dynamic_free(vct_ctx* c);
+// volumetric fog (vct_fog.hip): the context's scatter volume was built from the current pyramid;
+// release with the context
+inline bool fog_current(const vct_ctx* c) {
+    return c->fog.built && c->grid.voxelized && c->grid.mipped && c->fog.epoch == c->grid_epoch &&
+           c->fog.serial == c->grid.mips_serial;
+}
+void fog_free(vct_ctx* c);
 // ray reordering (variant 0x8000, vct_reorder.hip): *perm = the frame's pixels sorted by the
 // Morton code of their cone origin's voxel, background last (device, w * h entries)
 // (perm_spec, nullable: a second order for the specular part, by cell and cone aperture)

@@ -8,6 +8,7 @@
 #include <cmath>
 #include <string>
 #include "vct_internal.h"
+#include "vct_view.h"
 
 namespace vct {
 namespace {
@@ -89,12 +90,7 @@ __device__ __forceinline__ float dda_lim(const unsigned long long* __restrict__ 
     }
 }
 
-__device__ __forceinline__ uint32_t to8(float v) {   // Reinhard, gamma 1/2.2, round half away
-    v = v / (1.0f + v);
-    v = powf(v < 0.0f ? 0.0f : v, VCT_INV_GAMMA);
-    const int q = (int)lroundf(v * 255.0f);
-    return (uint32_t)(q < 0 ? 0 : (q > 255 ? 255 : q));
-}
+// the present step's tone curve, to8, is vct_view.h's
 
 // ---- host side --------------------------------------------------------------------------
 bool finite3(const float* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }

@@ -628,6 +628,7 @@ hipError_t launch_mips(vct_ctx* c) {
     Grid& g = c->grid;
     const bool zm_was_valid = g.zm_valid;
     g.zm_valid = false;
+    ++g.mips_serial;                            // a new pyramid: a fog volume of the previous one is stale
     const char* plan = getenv("VCT_K3_PLAN");   // A/B switches: read per call (k3_block_depth)
     const bool zmap_on = !env_off("VCT_ZMAP");
     g.zm_sh = env_off("VCT_ZMAP_EXACT") ? 1 : 0;   // A/B: the coarse test (map l+1 at c >> 1); both read the same maps

@@ -5,7 +5,7 @@
 //
 //   vct_headless <model.obj> [grid=256] [width=800] [height=600] [frames=5] [out.ppm] [devices=1]
 //                [--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32]
-//                [--light SPEC]... [--shadow-tan T] [--sky Z[:H[:G]]] [--mixed 2|4]
+//                [--light SPEC]... [--shadow-tan T] [--sky Z[:H[:G]]] [--mixed 2|4] [--fog DENSITY]
 //                [--dynamic FILE.obj [--dynamic-offset x,y,z]]
 //   (devices > 1: one process drives that many GPUs through vct_create_multi)
 //   --model: the model matrix of the reference's draw, T(0,-1.75,0) S(0.2)
@@ -24,6 +24,9 @@
 //   --mixed:  2 or 4: the frame is traced at mixed resolution (include/vct_mixed.h): diffuse cones on
 //            a frame that many times smaller per axis, upsampled, holes traced exactly, the
 //            specular cone at full resolution; absent: the full-resolution trace;
+//   --fog:    DENSITY > 0: volumetric fog (include/vct_fog.h) of that extinction per world unit, the
+//            other fields of the medium at the header's defaults: the scatter volume is built
+//            from the frame's lights, and the frame is the composite seen through the march;
 //   --dynamic: a second model, voxelized as the context's dynamic layer (include/vct_dynamic.h)
 //            on top of the first one's grid; Kd materials only (its diffuse maps are not loaded).
 //            --dynamic-offset: a world-space translation applied after the model matrix of
@@ -149,6 +152,7 @@ int main(int argc, char** argv) {
     bool has_sky = false;
     vct_sky sky{};
     uint32_t mixed = 0;
+    float fog_density = 0.0f;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--model=reference") ref_model = true;
@@ -176,6 +180,15 @@ int main(int argc, char** argv) {
             if (v != "2" && v != "4") { std::fprintf(stderr, "malformed --mixed %s (2 or 4)\n", v.c_str()); return 2; }
             mixed = (uint32_t)(v[0] - '0');
         }
+        else if (a == "--fog" || a.rfind("--fog=", 0) == 0) {
+            const std::string v = a == "--fog" ? (i + 1 < argc ? argv[++i] : "") : a.substr(6);
+            char* end = nullptr;
+            fog_density = std::strtof(v.c_str(), &end);
+            if (v.empty() || *end || !(fog_density > 0.0f) || !std::isfinite(fog_density)) {
+                std::fprintf(stderr, "malformed --fog %s (a density > 0)\n", v.c_str());
+                return 2;
+            }
+        }
         else if (a == "--dynamic-offset" || a.rfind("--dynamic-offset=", 0) == 0) {
             const std::string spec = a == "--dynamic-offset" ? (i + 1 < argc ? argv[++i] : "") : a.substr(17);
             if (!parse_offset(spec, dyn_offset)) { std::fprintf(stderr, "malformed --dynamic-offset %s\n", spec.c_str()); return 2; }
@@ -191,7 +204,7 @@ int main(int argc, char** argv) {
     }
     if (pos.empty()) {
         std::fprintf(stderr, "usage: %s model.obj [grid] [width] [height] [frames] [out.ppm] [devices] "
-                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] [--sky Z[:H[:G]]] [--mixed 2|4] "
+                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] [--sky Z[:H[:G]]] [--mixed 2|4] [--fog DENSITY] "
                              "[--dynamic FILE.obj [--dynamic-offset x,y,z]] "
                              "[--light dir:d:rgb | point:p:rgb:range | spot:p:d:rgb:range:inner:outer]...\n",
                      argv[0]);
@@ -214,6 +227,7 @@ int main(int argc, char** argv) {
     s.has_sky = has_sky;
     s.sky = sky;
     s.mixed_factor = mixed;
+    s.fog_density = fog_density;
     if (ref_model) ReferenceModelMatrix(s.model);
 
     AssetsManager& A = AssetsManager::Instance();            // assets.cpp:22-45

@@ -38,6 +38,7 @@ ConeTraceRenderer::~ConeTraceRenderer() {
     vct_device_free(ctx_, counter_);
     if (vis_) vct_device_free(ctx_, vis_);
     if (sky_) vct_device_free(ctx_, sky_);
+    if (fog_) vct_device_free(ctx_, fog_);
     vct_destroy(ctx_);
 }
 
@@ -107,7 +108,35 @@ bool ConeTraceRenderer::relight() {
     if (!check(vct_build_mips(ctx_), "vct_build_mips")) return false;
     if (s_.has_sky && !check(vct_inject_sky(ctx_, &s_.sky), "vct_inject_sky")) return false;
     if (s_.bounces && !check(vct_inject_bounces(ctx_, s_.bounces), "vct_inject_bounces")) return false;
+    if (s_.fog_density > 0.0f) {   // the scatter volume of the finished pyramid, one visibility cone per light
+        const std::vector<vct_light> lights = frame_lights();
+        const std::vector<float> tan_half(lights.size(), VCT_FOG_DEFAULT_TAN);
+        const vct_fog f = fog();
+        if (!check(vct_build_fog(ctx_, &f, lights.data(), (uint32_t)lights.size(), tan_half.data()), "vct_build_fog"))
+            return false;
+    }
     return true;
+}
+
+std::vector<vct_light> ConeTraceRenderer::frame_lights() const {
+    std::vector<vct_light> lights = s_.lights;
+    if (lights.empty()) {     // the default directional light as a list of one
+        vct_light l{};
+        l.type = VCT_LIGHT_DIRECTIONAL;
+        for (int k = 0; k < 3; ++k) { l.direction[k] = s_.light_dir[k]; l.color[k] = s_.light_color[k]; }
+        lights.push_back(l);
+    }
+    return lights;
+}
+
+vct_fog ConeTraceRenderer::fog() const {
+    vct_fog f{};
+    f.density = s_.fog_density;
+    f.albedo[0] = f.albedo[1] = f.albedo[2] = VCT_FOG_DEFAULT_ALBEDO;
+    f.ambient = VCT_FOG_DEFAULT_AMBIENT;
+    f.level = s_.grid >= 16u ? VCT_FOG_DEFAULT_LEVEL : 1u;   // a volume needs four cells per axis
+    f.step = VCT_FOG_DEFAULT_STEP;
+    return f;
 }
 
 void ConeTraceRenderer::Render() {
@@ -120,6 +149,7 @@ void ConeTraceRenderer::Render() {
     auto cam = AssetsManager::Instance().ActiveCamera();
     if (!cam) return;
     const vct_camera vc = cam->ToVct();
+    cam_ = vc;
     if (!check(vct_gbuffer_raster_device(ctx_, &vc, s_.width, s_.height, s_.roughness, (float*)gb_[0],
                                          (float*)gb_[1], (float*)gb_[2]), "G-buffer"))
         return;
@@ -154,16 +184,31 @@ void ConeTraceRenderer::Render() {
 }
 
 vct_status ConeTraceRenderer::composite(float* lin, uint32_t* rgba) {
+    if (!(s_.fog_density > 0.0f)) return composite_surface(lin, rgba);
+    // fog: the surface composite's linear frame (ours when the caller only wants RGBA8), then the
+    // segments, the march and rgb = rgb * T + F on it
+    const size_t plane = (size_t)s_.width * s_.height * 16;
+    if (!fog_) {
+        const vct_status st = vct_device_alloc(ctx_, 3 * plane, &fog_);
+        if (st != VCT_OK) return st;
+    }
+    float* const ray = (float*)fog_;
+    float* const fog4 = (float*)((char*)fog_ + plane);
+    float* const frame = lin ? lin : (float*)((char*)fog_ + 2 * plane);
+    vct_status st = composite_surface(frame, nullptr);
+    if (st != VCT_OK) return st;
+    const vct_fog f = fog();
+    if ((st = vct_fog_rays_device(ctx_, &cam_, cam_.position, (const float*)gb_[0], s_.width, s_.height, ray)) != VCT_OK)
+        return st;
+    if ((st = vct_fog_march_device(ctx_, &f, cam_.position, ray, s_.width, s_.height, fog4, nullptr)) != VCT_OK) return st;
+    return vct_fog_apply_device(ctx_, fog4, s_.width, s_.height, frame, rgba);
+}
+
+vct_status ConeTraceRenderer::composite_surface(float* lin, uint32_t* rgba) {
     const float *pos = (const float*)gb_[0], *nrm = (const float*)gb_[1], *alb = (const float*)gb_[2];
     const float *diff = (const float*)out_[0], *spec = (const float*)out_[1];
     if (s_.shadow_tan > 0.0f) {   // soft shadows: V per (light, pixel) from shadow cones, then the composite over it
-        std::vector<vct_light> lights = s_.lights;
-        if (lights.empty()) {     // the default directional light as a list of one
-            vct_light l{};
-            l.type = VCT_LIGHT_DIRECTIONAL;
-            for (int k = 0; k < 3; ++k) { l.direction[k] = s_.light_dir[k]; l.color[k] = s_.light_color[k]; }
-            lights.push_back(l);
-        }
+        const std::vector<vct_light> lights = frame_lights();
         const std::vector<float> tan_half(lights.size(), s_.shadow_tan);
         const size_t need = lights.size() * (size_t)s_.width * s_.height * sizeof(float);
         if (need > vis_bytes_) {   // the planes stay with the renderer, as gb_ and out_ do

@@ -47,6 +47,11 @@ struct ConeTraceSettings {
     // with the header's default parameters -- diffuse cones on the low frame and the holes,
     // the specular cone at full resolution; 0: vct_trace_device
     uint32_t mixed_factor = 0;
+    // > 0: volumetric fog (include/vct_fog.h) of this density per world unit, the other fields
+    // of the medium at the header's defaults: the scatter volume is built from the frame's
+    // lights after every relight, and every composite is followed by the view-ray march and
+    // the apply; 0: no fog, the frame is the surface composite's
+    float fog_density = 0.0f;
     // a sky (include/vct_sky.h): injected per voxel after the mips and before the bounces
     // (vct_inject_sky), and added per pixel to the diffuse plane after K4 (vct_sky_cones_device),
     // so every composite shows it through albedo x diffuse
@@ -88,6 +93,9 @@ private:
     bool relight();                       // inject -> mips (-> sky, bounces), as after every voxelization
     // row f3 into `lin` (float4) or `rgba` (packed 8-bit), with the light list when there is one
     vct_status composite(float* lin, uint32_t* rgba);
+    vct_status composite_surface(float* lin, uint32_t* rgba);   // the composite without the fog
+    std::vector<vct_light> frame_lights() const;                // the light list, or the default light as one
+    vct_fog fog() const;                                        // fog_density with the header defaults
 
     std::string model_name_;
     ConeTraceSettings s_;
@@ -98,6 +106,8 @@ private:
     void* vis_ = nullptr;                 // V planes of the soft-shadow composite (shadow_tan > 0), kept
     size_t vis_bytes_ = 0;
     void* sky_ = nullptr;                 // (Sk.rgb, vis) plane of the frame's sky call (has_sky), kept
+    void* fog_ = nullptr;                 // ray, fog and linear planes of the fog pass (fog_density > 0), kept
+    vct_camera cam_{};                    // the camera of the last Render(), for the fog's background rays
     bool scene_dirty_ = true;
     bool dynamic_dirty_ = true;           // the dynamic matrix changed since the layer was voxelized
     vct_status status_ = VCT_OK;

@@ -30,10 +30,11 @@ import numpy as np
 from . import _lib
 from ._lib import VCT_ALL_RANKS, VctCamera, VctCommId, VctConfig, VctLight, VctSky, VctTexture, VctTraceArgs
 from ._lib import VCT_CONES_DIFFUSE, VCT_CONES_SPECULAR, VctMixedHoles, VctMixedParams
+from ._lib import VctFog
 
 __all__ = ["Context", "VctError", "VctConfig", "VctCamera", "tiles_for_rank", "tile_offset", "VERTEX_FLOATS",
            "VCT_ALL_RANKS", "comm_frame_layout", "VctLight", "directional_light", "point_light", "spot_light",
-           "VctSky", "sky_light", "VctMixedParams", "VctMixedHoles", "VCT_CONES_DIFFUSE", "VCT_CONES_SPECULAR"]
+           "VctSky", "sky_light", "VctFog", "fog", "VctMixedParams", "VctMixedHoles", "VCT_CONES_DIFFUSE", "VCT_CONES_SPECULAR"]
 
 VERTEX_FLOATS = 14          # reference Vertex: Position, Normal, TexCoords, Tangent, Bitangent
 VERTEX_STRIDE = VERTEX_FLOATS * 4
@@ -92,6 +93,17 @@ def sky_light(zenith, horizon=None, ground=None, up=(0.0, 1.0, 0.0)) -> VctSky:
     s.horizon = _f3(zenith if horizon is None else horizon)
     s.ground = _f3((0.0, 0.0, 0.0) if ground is None else ground)
     return s
+
+
+def fog(density, albedo=(_lib.VCT_FOG_DEFAULT_ALBEDO,) * 3, ambient=0.0, level=_lib.VCT_FOG_DEFAULT_LEVEL,
+        step=_lib.VCT_FOG_DEFAULT_STEP) -> VctFog:
+    """A vct_fog: `density` is the extinction per world unit, `albedo` the single-scattering
+    albedo, `ambient` the weight of the cone-traced indirect term (0: off), one cell of the
+    scatter volume is 2^level voxels and the march steps `step` cells.  The fields are checked
+    against the grid when a context uses the record (_lib.check_fog, the library's own rule)."""
+    f = VctFog()
+    f.density, f.albedo, f.ambient, f.level, f.step = float(density), _f3(albedo), float(ambient), int(level), float(step)
+    return f
 
 
 def _light_array(lights):
@@ -598,6 +610,70 @@ class Context:
         if not isinstance(sky, VctSky):
             raise VctError(_EINVAL, f"inject_sky: expected a VctSky (vct.sky_light), got {type(sky).__name__}")
         self._check(fn(self.h, C.byref(sky)), "inject_sky")
+
+    # -- volumetric fog (include/vct_fog.h) ----------------------------------
+    def _fog(self, fog, what):
+        if not isinstance(fog, VctFog):
+            raise VctError(_EINVAL, f"{what}: expected a VctFog (vct.fog), got {type(fog).__name__}")
+        bad = _lib.check_fog(fog.density, tuple(fog.albedo), fog.ambient, fog.level, fog.step, self.n, self.extent)
+        if bad:
+            raise VctError(_EINVAL, f"{what}: {bad}")
+        return C.byref(fog)
+
+    def build_fog(self, fog, lights=(), tan_half=None):
+        """vct_build_fog: the scatter volume of `fog` (vct.fog) from the current pyramid, lit by
+        `lights` through one visibility cone each (tan_half: one aperture per light, default
+        VCT_FOG_DEFAULT_TAN).  After build_mips (and any inject_sky / inject_bounces)."""
+        fn = _lib.bind_fog_extension(self.lib, "vct_build_fog")
+        ref = self._fog(fog, "build_fog")
+        arr, n = _light_array(lights)
+        th = [_lib.VCT_FOG_DEFAULT_TAN] * n if tan_half is None else [float(t) for t in tan_half]
+        if len(th) != n:
+            raise VctError(_EINVAL, f"build_fog: {len(th)} apertures for {n} lights")
+        self._check(fn(self.h, ref, arr, n, (C.c_float * max(n, 1))(*th)), "build_fog")
+
+    def fog_dims(self) -> int:
+        """vct_fog_dims: the cell count m of the current scatter volume."""
+        m = C.c_uint32()
+        self._check(_lib.bind_fog_extension(self.lib, "vct_fog_dims")(self.h, C.byref(m)), "fog_dims")
+        return int(m.value)
+
+    def download_fog(self) -> np.ndarray:
+        """vct_download_fog: the scatter volume as [m, m, m, 4] float32 (z, y, x)."""
+        m = self.fog_dims()
+        out = np.empty((m, m, m, 4), np.float32)
+        self._check(_lib.bind_fog_extension(self.lib, "vct_download_fog")(self.h, _fptr(out)), "download_fog")
+        return out
+
+    def fog_rays_device(self, cam, eye, pos4, width, height, ray4):
+        """vct_fog_rays_device: (d.xyz, len) per pixel in voxel units into ray4, a float32 device
+        tensor [height, width, 4].  cam: a VctCamera (background pixels get their primary ray) or
+        None (background pixels get a null record)."""
+        fn = _lib.bind_fog_extension(self.lib, "vct_fog_rays_device")
+        if hasattr(cam, "to_ctypes"):
+            cam = cam.to_ctypes()
+        if cam is not None and not isinstance(cam, VctCamera):
+            raise VctError(_EINVAL, f"fog_rays: expected a camera or None, got {type(cam).__name__}")
+        n = 4 * width * height
+        self._check(fn(self.h, None if cam is None else C.byref(cam), _f3(eye), self._dev(pos4, "pos4", _F32, n),
+                       width, height, self._dev(ray4, "ray4", _F32, n)), "fog_rays")
+
+    def fog_march_device(self, fog, eye, ray4, width, height, fog4, steps=None):
+        """vct_fog_march_device: (F.rgb, T) per pixel into fog4, a float32 device tensor
+        [height, width, 4].  steps: a 1-element int64 device tensor the call adds its samples to."""
+        fn = _lib.bind_fog_extension(self.lib, "vct_fog_march_device")
+        n = 4 * width * height
+        self._check(fn(self.h, self._fog(fog, "fog_march"), _f3(eye), self._dev(ray4, "ray4", _F32, n), width, height,
+                       self._dev(fog4, "fog4", _F32, n), self._dev(steps, "steps", _I64, 1)), "fog_march")
+
+    def fog_apply_device(self, fog4, width, height, linear4_inout=None, out_rgba8=None):
+        """vct_fog_apply_device: rgb = fmaf(rgb, T, F) on a composite's linear frame, and / or the
+        RGBA8 frame of the result."""
+        fn = _lib.bind_fog_extension(self.lib, "vct_fog_apply_device")
+        n = 4 * width * height
+        self._check(fn(self.h, self._dev(fog4, "fog4", _F32, n), width, height,
+                       self._dev(linear4_inout, "linear4_inout", _F32, n),
+                       self._dev(out_rgba8, "out_rgba8", _I32, width * height)), "fog_apply")
 
     # -- mixed-resolution trace (include/vct_mixed.h) ------------------------
     def mixed_params(self, factor, normal_cos=None, plane_eps=None, max_holes=0) -> VctMixedParams:

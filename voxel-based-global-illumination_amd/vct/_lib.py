@@ -61,6 +61,12 @@ VCT_MIXED_NORMAL_COS = 0.9
 VCT_MIXED_HOLE_WIDTH = 64
 VCT_MIXED_NO_SOURCE = 0xFFFFFFFF
 
+# include/vct_fog.h: volumetric fog, likewise HIP only (bind_fog_extension)
+FOG_EXTENSIONS = ("vct_build_fog", "vct_fog_dims", "vct_download_fog", "vct_fog_rays_device", "vct_fog_march_device",
+                  "vct_fog_apply_device")
+VCT_FOG_DENSITY_LIMIT = 2.0 ** 20
+VCT_FOG_DEFAULT_ALBEDO, VCT_FOG_DEFAULT_LEVEL, VCT_FOG_DEFAULT_STEP, VCT_FOG_DEFAULT_TAN = 0.9, 2, 1.0, 0.1
+
 STATUS = {0: "VCT_OK", 1: "VCT_EINVAL", 2: "VCT_ENOMEM", 3: "VCT_EDEVICE", 4: "VCT_ECOMM", 5: "VCT_ESTATE"}
 
 
@@ -112,6 +118,47 @@ class VctSky(C.Structure):            # vct_sky, 48 bytes
         ("horizon", C.c_float * 3),
         ("ground", C.c_float * 3),
     ]
+
+
+class VctFog(C.Structure):            # vct_fog, 28 bytes
+    _fields_ = [
+        ("density", C.c_float),
+        ("albedo", C.c_float * 3),
+        ("ambient", C.c_float),
+        ("level", C.c_uint32),
+        ("step", C.c_float),
+    ]
+
+
+def check_fog(density, albedo, ambient, level, step, n, extent):
+    """The input rule of include/vct_fog.h (vct_spec.h "volumetric fog") for a grid of n^3
+    voxels and edge `extent`, in float32 as the library tests it: None, or what is wrong.
+    The binding and the tests share it; the library applies the same rule itself."""
+    import numpy as np
+    F = np.float32
+    with np.errstate(all="ignore"):
+        d = F(density)
+        if not np.isfinite(d) or np.signbit(d):
+            return "density must be finite with a clear sign bit"
+        if d > F(VCT_FOG_DENSITY_LIMIT):
+            return "density above VCT_FOG_DENSITY_LIMIT"
+        if len(albedo) != 3:
+            return "albedo must have three components"
+        for a in albedo:
+            a = F(a)
+            if not np.isfinite(a) or np.signbit(a) or a > F(1.0):
+                return "albedo must be finite and in [0, 1] (-0.0f is refused)"
+        am = F(ambient)
+        if not np.isfinite(am) or not am >= F(0.0):
+            return "ambient must be finite and >= 0"
+        if int(level) != level or not 1 <= int(level) <= 31 or (int(n) >> int(level)) < 4:
+            return "level must satisfy 1 <= level and (n >> level) >= 4"
+        st = F(step)
+        if not (st >= F(0.25) and st <= F(4.0)):
+            return "step must be in [0.25, 4]"
+        if not np.isfinite((d * F(extent)) / F(n)):
+            return "density * extent overflows"
+    return None
 
 
 class VctMixedParams(C.Structure):    # vct_mixed_params, 16 bytes
@@ -328,6 +375,43 @@ def bind_emission_extension(lib: C.CDLL, name: str):
     fn.restype = res
     fn.argtypes = args
     return fn
+
+
+def bind_fog_extension(lib: C.CDLL, name: str):
+    """The include/vct_fog.h function `name` of `lib`, with its signature declared;
+    AttributeError (naming the library) if this implementation does not export it."""
+    P, u32, i32 = C.c_void_p, C.c_uint32, C.c_int32
+    F3 = C.POINTER(C.c_float)
+    sig = {
+        "vct_build_fog": (i32, [P, C.POINTER(VctFog), C.POINTER(VctLight), u32, F3]),
+        "vct_fog_dims": (i32, [P, C.POINTER(u32)]),
+        "vct_download_fog": (i32, [P, P]),
+        "vct_fog_rays_device": (i32, [P, C.POINTER(VctCamera), F3, P, u32, u32, P]),
+        "vct_fog_march_device": (i32, [P, C.POINTER(VctFog), F3, P, u32, u32, P, P]),
+        "vct_fog_apply_device": (i32, [P, P, u32, u32, P, P]),
+    }
+    res, args = sig[name]
+    try:
+        fn = getattr(lib, name)
+    except AttributeError:
+        raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
+                             "(include/vct_fog.h is implemented by the HIP library only)") from None
+    fn.restype = res
+    fn.argtypes = args
+    return fn
+
+
+def debug_fog(lib: C.CDLL, handle=None, force64: int = -1, counters=None) -> int:
+    """Test hook (vct_debug_fog, not part of the headers).  force64 >= 0, process-wide: nonzero
+    sends the light cones of every fog build through the 64-bit-address path (the one 1024^3
+    takes).  counters: None, or (light_steps, ambient_steps) device pointers (ints, 0: none) of
+    8-byte counters the context's following builds add their light-cone and ambient K4 steps
+    to.  -> the address path of the context's last build: 32, 64, 0 before any."""
+    fn = lib.vct_debug_fog
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    a, b = counters if counters is not None else (0, 0)
+    return int(fn(handle, int(force64), 0 if counters is None else 1, a or None, b or None))
 
 
 def bind_sky_extension(lib: C.CDLL, name: str):
