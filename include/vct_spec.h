@@ -551,4 +551,50 @@
                                                  1024^3 at level 1, step 0.25 (3548 samples) */
 #define VCT_FOG_DENSITY_LIMIT  1048576.0f     /* 2^20 per world unit                         */
 
+/* ---- temporal accumulation (include/vct_temporal.h; tests/temporal_ref.py restates it) ----
+ *  All arithmetic is float32, one rounding per operation, no contraction; integers are exact.
+ *    dot3 is "local lights"'.  Per pixel (x, y) of a w x h frame with records P, N, the planes'
+ *    values cur_p (p < n_planes), and, with a history, last frame's camera (eye', front', right',
+ *    up', tan_half, aspect: the host constants of vct_view.h camera_fields for this w and h,
+ *    tan_half = tanf(zoom_deg * 0.5f * 3.14159265358979f / 180.0f), aspect = (float)w / (float)h),
+ *    last frame's records Pq, Nq, planes hist_p and lengths hist_len.
+ *  Background (P.w == 0): +0 in every channel of every out_p, out_len = 0; not counted.
+ *  Reset: out_p = cur_p bit for bit in every plane, out_len = 1.  A valid pixel is counted in
+ *    exactly one of reused, reset_offscreen and reset_rejected; valid is their sum.
+ *    reset_offscreen: no history (prev_cam == NULL); motion4.w == 0; a failed projection test.
+ *    reset_rejected: no accepted tap (W = 0); a non-finite blended history; k = 1 (max_len = 1).
+ *  Previous position: q = motion4.xyz, or P.xyz when motion4 is NULL (a NaN motion4.w is not 0).
+ *  Projection (the inverse of vct_view.h pixel_ray):
+ *      v_c = q_c - eye'_c,  z = dot3(v, front'),  a = dot3(v, right'),  b = dot3(v, up')
+ *    reset unless z > 0;
+ *      kx = tan_half * aspect,  sx = a / (z * kx),  sy = b / (z * tan_half)
+ *      fx = ((sx + 1.0f) * 0.5f) * (float)w - 0.5f,  fy = ((1.0f - sy) * 0.5f) * (float)h - 0.5f
+ *    reset unless -1.0f < fx < (float)w and -1.0f < fy < (float)h.  A NaN fails every comparison;
+ *    the comparisons also make the integer conversions below safe.
+ *  Taps, in integers, in x and likewise in y:
+ *      X16 = (int)floorf(fx * 16.0f + 0.5f),  x0 = X16 >> 4 (floor: -1 .. w),  rx = X16 & 15,
+ *      tap x0 weighs 16 - rx, tap x0 + 1 weighs rx;  bw = (x weight) (y weight), summing to 256.
+ *    Taps are visited in the order (0,0), (1,0), (0,1), (1,1).  A tap is dropped when it lies
+ *    outside the frame, bw = 0, its Pq.w == 0, or its hist_len == 0.  A remaining tap is
+ *    accepted when both
+ *      c = dot3(N, Nq) >= normal_cos
+ *      d = |dot3(N, Pq - q)| <= plane_eps        (Pq - q per component, then the dot3)
+ *    hold; a NaN fails either test.
+ *  Blended history, per plane and channel, by the upsample's rule: S = bw hist of the first
+ *    accepted tap, then S = S + bw hist for each further one (bw converted to float, one
+ *    multiply, one add); W = float(integer sum of the accepted bw); H = S / W, one correctly
+ *    rounded division.  W = 0 is a reset.  If any of the 4 n_planes values of H is not finite the
+ *    pixel resets, so one bad sample cannot poison a pixel for ever.
+ *  Blend: L = min of hist_len over the accepted taps (>= 1), k = min(L, max_len - 1) + 1, which
+ *    is min(L + 1, max_len) without the overflow.  k = 1: a reset (H + (cur - H) * 1 is not cur
+ *    in floats).  Otherwise wk = 1.0f / (float)k and
+ *      out = H + (cur - H) * wk                  (subtract, multiply, add)
+ *    out_len = k, and the pixel counts as reused.
+ *  A single tap of bw = 256 gives H = hist exactly (256 hist and the division are exact unless
+ *    256 hist overflows, which resets), so under an unchanged camera and G-buffer a constant
+ *    input stays that constant: H + (c - H) * wk = c + 0 (a constant -0 becomes +0).
+ *  Input rule: normal_cos finite in [-1, 1]; plane_eps finite, >= 0, sign bit clear; max_len in
+ *    1 .. VCT_TEMPORAL_MAX_LEN; tan_half finite and > 0, every component of eye', front',
+ *    right', up' finite; anything else is VCT_EINVAL with nothing written. */
+
 #endif /* VCT_SPEC_H */

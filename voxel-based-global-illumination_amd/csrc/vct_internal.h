@@ -204,8 +204,10 @@ struct Fog {
 // concurrently (a host that overlaps consecutive frames), so the cone-split hand-over
 // and the ray-reorder buffers belong to the stream, not to the context.
 // (vct_mixed.hip adds three: the plane a cone selection does not ask for, the upsample's hole
-// mask and row counts, and the frame call's low and hole frames)
-enum { kScFlags = 0, kScHand = 1, kScKeys = 2, kScSort = 3, kScOrder = 4, kScUnsel = 5, kScMixUp = 6, kScMixed = 7, kScN = 8 };
+// mask and row counts, and the frame call's low and hole frames; vct_temporal.hip one: the
+// per-wave stats words)
+enum { kScFlags = 0, kScHand = 1, kScKeys = 2, kScSort = 3, kScOrder = 4, kScUnsel = 5, kScMixUp = 6, kScMixed = 7,
+       kScTemporal = 8, kScN = 9 };
 struct StreamScratch {
     hipStream_t s = nullptr;
     bool used = false;

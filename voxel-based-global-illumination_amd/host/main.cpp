@@ -6,7 +6,7 @@
 //   vct_headless <model.obj> [grid=256] [width=800] [height=600] [frames=5] [out.ppm] [devices=1]
 //                [--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32]
 //                [--light SPEC]... [--shadow-tan T] [--sky Z[:H[:G]]] [--mixed 2|4] [--fog DENSITY]
-//                [--dynamic FILE.obj [--dynamic-offset x,y,z]]
+//                [--temporal N] [--dynamic FILE.obj [--dynamic-offset x,y,z]]
 //   (devices > 1: one process drives that many GPUs through vct_create_multi)
 //   --model: the model matrix of the reference's draw, T(0,-1.75,0) S(0.2)
 //            (r_voxelization.cpp:26-29; default), or none;
@@ -27,6 +27,10 @@
 //   --fog:    DENSITY > 0: volumetric fog (include/vct_fog.h) of that extinction per world unit, the
 //            other fields of the medium at the header's defaults: the scatter volume is built
 //            from the frame's lights, and the frame is the composite seen through the march;
+//   --temporal: N in 1 .. 1024: temporal accumulation (include/vct_temporal.h): every frame blends its
+//            diffuse plane with the reprojected history of the frame before it, a running mean of at
+//            most N frames, the other parameters at the header's defaults, and the composite reads
+//            the accumulated plane; absent: every frame stands alone;
 //   --dynamic: a second model, voxelized as the context's dynamic layer (include/vct_dynamic.h)
 //            on top of the first one's grid; Kd materials only (its diffuse maps are not loaded).
 //            --dynamic-offset: a world-space translation applied after the model matrix of
@@ -153,6 +157,7 @@ int main(int argc, char** argv) {
     vct_sky sky{};
     uint32_t mixed = 0;
     float fog_density = 0.0f;
+    uint32_t temporal = 0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--model=reference") ref_model = true;
@@ -189,6 +194,16 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
+        else if (a == "--temporal" || a.rfind("--temporal=", 0) == 0) {
+            const std::string v = a == "--temporal" ? (i + 1 < argc ? argv[++i] : "") : a.substr(11);
+            char* end = nullptr;
+            const long t = std::strtol(v.c_str(), &end, 10);
+            if (v.empty() || v[0] < '0' || v[0] > '9' || *end || t < 1 || t > (long)VCT_TEMPORAL_MAX_LEN) {
+                std::fprintf(stderr, "malformed --temporal %s (1 .. %u)\n", v.c_str(), VCT_TEMPORAL_MAX_LEN);
+                return 2;
+            }
+            temporal = (uint32_t)t;
+        }
         else if (a == "--dynamic-offset" || a.rfind("--dynamic-offset=", 0) == 0) {
             const std::string spec = a == "--dynamic-offset" ? (i + 1 < argc ? argv[++i] : "") : a.substr(17);
             if (!parse_offset(spec, dyn_offset)) { std::fprintf(stderr, "malformed --dynamic-offset %s\n", spec.c_str()); return 2; }
@@ -204,7 +219,7 @@ int main(int argc, char** argv) {
     }
     if (pos.empty()) {
         std::fprintf(stderr, "usage: %s model.obj [grid] [width] [height] [frames] [out.ppm] [devices] "
-                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] [--sky Z[:H[:G]]] [--mixed 2|4] [--fog DENSITY] "
+                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] [--sky Z[:H[:G]]] [--mixed 2|4] [--fog DENSITY] [--temporal N] "
                              "[--dynamic FILE.obj [--dynamic-offset x,y,z]] "
                              "[--light dir:d:rgb | point:p:rgb:range | spot:p:d:rgb:range:inner:outer]...\n",
                      argv[0]);
@@ -228,6 +243,7 @@ int main(int argc, char** argv) {
     s.sky = sky;
     s.mixed_factor = mixed;
     s.fog_density = fog_density;
+    s.temporal_len = temporal;
     if (ref_model) ReferenceModelMatrix(s.model);
 
     AssetsManager& A = AssetsManager::Instance();            // assets.cpp:22-45

@@ -1,6 +1,7 @@
 // renderer.cpp — ConeTraceRenderer: the reference's Renderer slot driving the VCT C-ABI.
 #include "renderer.h"
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstddef>
@@ -28,7 +29,15 @@ ConeTraceRenderer::ConeTraceRenderer(const std::string& model_name, const ConeTr
         if (!check(vct_device_alloc(ctx_, fb, &p), "alloc gbuffer")) return;
     for (auto& p : out_)
         if (!check(vct_device_alloc(ctx_, fb, &p), "alloc output")) return;
-    check(vct_device_alloc(ctx_, 8, &counter_), "alloc counter");
+    if (!check(vct_device_alloc(ctx_, 8, &counter_), "alloc counter")) return;
+    if (s.temporal_len) {
+        for (auto& p : hist_)
+            if (!check(vct_device_alloc(ctx_, fb, &p), "alloc history plane")) return;
+        for (auto& p : hist_len_)
+            if (!check(vct_device_alloc(ctx_, fb / 4, &p), "alloc history lengths")) return;
+        for (auto& p : prev_gb_)
+            if (!check(vct_device_alloc(ctx_, fb, &p), "alloc previous gbuffer")) return;
+    }
 }
 
 ConeTraceRenderer::~ConeTraceRenderer() {
@@ -39,6 +48,9 @@ ConeTraceRenderer::~ConeTraceRenderer() {
     if (vis_) vct_device_free(ctx_, vis_);
     if (sky_) vct_device_free(ctx_, sky_);
     if (fog_) vct_device_free(ctx_, fog_);
+    for (void* p : hist_) if (p) vct_device_free(ctx_, p);
+    for (void* p : hist_len_) if (p) vct_device_free(ctx_, p);
+    for (void* p : prev_gb_) if (p) vct_device_free(ctx_, p);
     vct_destroy(ctx_);
 }
 
@@ -150,6 +162,10 @@ void ConeTraceRenderer::Render() {
     if (!cam) return;
     const vct_camera vc = cam->ToVct();
     cam_ = vc;
+    if (s_.temporal_len && has_prev_) {   // the last frame's G-buffer stays; this frame's goes to the other pair
+        std::swap(gb_[0], prev_gb_[0]);
+        std::swap(gb_[1], prev_gb_[1]);
+    }
     if (!check(vct_gbuffer_raster_device(ctx_, &vc, s_.width, s_.height, s_.roughness, (float*)gb_[0],
                                          (float*)gb_[1], (float*)gb_[2]), "G-buffer"))
         return;
@@ -181,6 +197,35 @@ void ConeTraceRenderer::Render() {
         check(vct_sky_cones_device(ctx_, a.pos4, a.nrm4, s_.width, s_.height, &s_.sky, (float*)sky_, a.diffuse4, nullptr),
               "vct_sky_cones_device");
     }
+    if (s_.temporal_len && status_ == VCT_OK) accumulate_diffuse();
+}
+
+bool ConeTraceRenderer::accumulate_diffuse() {
+    vct_temporal_params tp{};
+    if (!check(vct_temporal_default_params(ctx_, &tp), "vct_temporal_default_params")) return false;
+    tp.max_len = s_.temporal_len;
+    const int now = has_prev_ ? 1 - hist_cur_ : hist_cur_;
+    vct_temporal_args t{};
+    t.width = s_.width;
+    t.height = s_.height;
+    t.pos4 = (const float*)gb_[0];
+    t.nrm4 = (const float*)gb_[1];
+    if (has_prev_) {
+        t.prev_cam = &prev_cam_;
+        t.prev_pos4 = (const float*)prev_gb_[0];
+        t.prev_nrm4 = (const float*)prev_gb_[1];
+        t.hist4[0] = (const float*)hist_[1 - now];
+        t.hist_len = (const uint32_t*)hist_len_[1 - now];
+    }
+    t.n_planes = 1;
+    t.cur4[0] = (const float*)out_[0];
+    t.out4[0] = (float*)hist_[now];
+    t.out_len = (uint32_t*)hist_len_[now];
+    if (!check(vct_temporal_accumulate_device(ctx_, &t, &tp), "vct_temporal_accumulate_device")) return false;
+    prev_cam_ = cam_;
+    has_prev_ = true;
+    hist_cur_ = now;
+    return true;
 }
 
 vct_status ConeTraceRenderer::composite(float* lin, uint32_t* rgba) {
@@ -206,7 +251,8 @@ vct_status ConeTraceRenderer::composite(float* lin, uint32_t* rgba) {
 
 vct_status ConeTraceRenderer::composite_surface(float* lin, uint32_t* rgba) {
     const float *pos = (const float*)gb_[0], *nrm = (const float*)gb_[1], *alb = (const float*)gb_[2];
-    const float *diff = (const float*)out_[0], *spec = (const float*)out_[1];
+    const float* diff = (const float*)(s_.temporal_len && has_prev_ ? hist_[hist_cur_] : out_[0]);   // the accumulated plane
+    const float* spec = (const float*)out_[1];
     if (s_.shadow_tan > 0.0f) {   // soft shadows: V per (light, pixel) from shadow cones, then the composite over it
         const std::vector<vct_light> lights = frame_lights();
         const std::vector<float> tan_half(lights.size(), s_.shadow_tan);

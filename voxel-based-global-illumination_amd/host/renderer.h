@@ -52,6 +52,12 @@ struct ConeTraceSettings {
     // lights after every relight, and every composite is followed by the view-ray march and
     // the apply; 0: no fog, the frame is the surface composite's
     float fog_density = 0.0f;
+    // > 0: temporal accumulation (include/vct_temporal.h) of the diffuse plane over a running
+    // mean of at most this many frames (max_len, 1 .. VCT_TEMPORAL_MAX_LEN), the other
+    // parameters at the header's defaults: after K4 (and the sky) every frame blends its
+    // diffuse plane with the reprojected history of the previous Render(), and the composite
+    // reads the accumulated plane; 0: every frame stands alone
+    uint32_t temporal_len = 0;
     // a sky (include/vct_sky.h): injected per voxel after the mips and before the bounces
     // (vct_inject_sky), and added per pixel to the diffuse plane after K4 (vct_sky_cones_device),
     // so every composite shows it through albedo x diffuse
@@ -108,6 +114,16 @@ private:
     void* sky_ = nullptr;                 // (Sk.rgb, vis) plane of the frame's sky call (has_sky), kept
     void* fog_ = nullptr;                 // ray, fog and linear planes of the fog pass (fog_density > 0), kept
     vct_camera cam_{};                    // the camera of the last Render(), for the fog's background rays
+    // temporal accumulation (temporal_len > 0): the accumulated diffuse planes and history lengths of
+    // this frame and the last one (hist_cur_: this frame's), and the last frame's position and normal
+    // planes and camera; gb_[0..1] and prev_gb_ swap every frame instead of being copied
+    bool accumulate_diffuse();
+    void* hist_[2] = {nullptr, nullptr};
+    void* hist_len_[2] = {nullptr, nullptr};
+    void* prev_gb_[2] = {nullptr, nullptr};
+    vct_camera prev_cam_{};
+    bool has_prev_ = false;               // prev_gb_, prev_cam_ and hist_[1 - hist_cur_] hold a frame
+    int hist_cur_ = 0;
     bool scene_dirty_ = true;
     bool dynamic_dirty_ = true;           // the dynamic matrix changed since the layer was voxelized
     vct_status status_ = VCT_OK;

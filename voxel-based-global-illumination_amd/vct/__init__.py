@@ -31,8 +31,9 @@ from . import _lib
 from ._lib import VCT_ALL_RANKS, VctCamera, VctCommId, VctConfig, VctLight, VctSky, VctTexture, VctTraceArgs
 from ._lib import VCT_CONES_DIFFUSE, VCT_CONES_SPECULAR, VctMixedHoles, VctMixedParams
 from ._lib import VctFog
+from ._lib import VctTemporalArgs, VctTemporalParams
 
-__all__ = ["Context", "VctError", "VctConfig", "VctCamera", "tiles_for_rank", "tile_offset", "VERTEX_FLOATS",
+__all__ = ["VctTemporalParams","Context", "VctError", "VctConfig", "VctCamera", "tiles_for_rank", "tile_offset", "VERTEX_FLOATS",
            "VCT_ALL_RANKS", "comm_frame_layout", "VctLight", "directional_light", "point_light", "spot_light",
            "VctSky", "sky_light", "VctFog", "fog", "VctMixedParams", "VctMixedHoles", "VCT_CONES_DIFFUSE", "VCT_CONES_SPECULAR"]
 
@@ -791,6 +792,58 @@ class Context:
         a = self._mixed_args(pos4, nrm4, alb4, width, height, eye, diffuse4, spec4, steps_px, cone_steps,
                              texel_fetches, tile_rank, tile_world, tile_compact, variant)
         self._check(fn(self.h, C.byref(a), C.byref(params)), "trace_mixed_device")
+
+    # -- temporal accumulation (include/vct_temporal.h) -----------------------
+    def temporal_params(self, normal_cos=None, plane_eps=None, max_len=None) -> VctTemporalParams:
+        """A vct_temporal_params: the header defaults of this context
+        (vct_temporal_default_params), with the fields given replaced."""
+        p = VctTemporalParams()
+        self._check(_lib.bind_temporal_extension(self.lib, "vct_temporal_default_params")(self.h, C.byref(p)),
+                    "temporal_default_params")
+        if normal_cos is not None:
+            p.normal_cos = normal_cos
+        if plane_eps is not None:
+            p.plane_eps = plane_eps
+        if max_len is not None:
+            p.max_len = max_len
+        return p
+
+    def temporal_accumulate_device(self, params, pos4, nrm4, width, height, cur, out, out_len, prev_cam=None,
+                                   prev_pos4=None, prev_nrm4=None, hist=None, hist_len=None, motion4=None,
+                                   stats=None, n_planes=None):
+        """vct_temporal_accumulate_device.  cur / hist / out: sequences of up to four float32
+        device tensors [height, width, 4] (this frame's planes, last frame's accumulated planes,
+        this frame's accumulated planes; out[p] may be cur[p]); hist_len / out_len: int32 or
+        uint32 device tensors [height, width]; prev_cam: last frame's camera, or None for a
+        frame without history (hist, hist_len and the previous G-buffer are then not read);
+        motion4: None, or where each pixel's surface point was last frame (w = 0: nowhere);
+        stats: None, or 4 int32 {valid, reused, reset_offscreen, reset_rejected}.
+        n_planes: len(cur) unless given."""
+        fn = _lib.bind_temporal_extension(self.lib, "vct_temporal_accumulate_device")
+        if not isinstance(params, VctTemporalParams):
+            raise VctError(_EINVAL, "temporal_accumulate: expected a VctTemporalParams (Context.temporal_params)")
+        if hasattr(prev_cam, "to_ctypes"):
+            prev_cam = prev_cam.to_ctypes()
+        if prev_cam is not None and not isinstance(prev_cam, VctCamera):
+            raise VctError(_EINVAL, f"temporal_accumulate: expected a camera or None, got {type(prev_cam).__name__}")
+        cur, out, hist = list(cur), list(out), list(hist or [])
+        if max(len(cur), len(out), len(hist)) > 4:
+            raise VctError(_EINVAL, "temporal_accumulate: more than four planes")
+        n, px = 4 * width * height, width * height
+        a = VctTemporalArgs()
+        a.width, a.height = width, height
+        a.pos4, a.nrm4 = self._dev(pos4, "pos4", _F32, n), self._dev(nrm4, "nrm4", _F32, n)
+        a.motion4 = self._dev(motion4, "motion4", _F32, n)
+        a.prev_cam = C.pointer(prev_cam) if prev_cam is not None else None
+        a.prev_pos4, a.prev_nrm4 = self._dev(prev_pos4, "prev_pos4", _F32, n), self._dev(prev_nrm4, "prev_nrm4", _F32, n)
+        a.n_planes = len(cur) if n_planes is None else n_planes
+        for name, field, planes in (("cur", a.cur4, cur), ("hist", a.hist4, hist), ("out", a.out4, out)):
+            for p, t in enumerate(planes):
+                field[p] = self._dev(t, f"{name}[{p}]", _F32, n)
+        a.hist_len = self._dev(hist_len, "hist_len", _I32, px)
+        a.out_len = self._dev(out_len, "out_len", _I32, px)
+        a.stats = self._dev(stats, "stats", _I32, 4)
+        self._check(fn(self.h, C.byref(a), C.byref(params)), "temporal_accumulate_device")
 
     # -- dynamic layer (include/vct_dynamic.h) --------------------------------
     def voxelize_dynamic(self, verts: np.ndarray, idx: np.ndarray, tri_material: np.ndarray | None = None,

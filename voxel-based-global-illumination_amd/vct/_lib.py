@@ -67,6 +67,10 @@ FOG_EXTENSIONS = ("vct_build_fog", "vct_fog_dims", "vct_download_fog", "vct_fog_
 VCT_FOG_DENSITY_LIMIT = 2.0 ** 20
 VCT_FOG_DEFAULT_ALBEDO, VCT_FOG_DEFAULT_LEVEL, VCT_FOG_DEFAULT_STEP, VCT_FOG_DEFAULT_TAN = 0.9, 2, 1.0, 0.1
 
+# include/vct_temporal.h: temporal accumulation, likewise HIP only (bind_temporal_extension)
+TEMPORAL_EXTENSIONS = ("vct_temporal_default_params", "vct_temporal_accumulate_device")
+VCT_TEMPORAL_DEFAULT_LEN, VCT_TEMPORAL_MAX_LEN = 8, 1024
+
 STATUS = {0: "VCT_OK", 1: "VCT_EINVAL", 2: "VCT_ENOMEM", 3: "VCT_EDEVICE", 4: "VCT_ECOMM", 5: "VCT_ESTATE"}
 
 
@@ -179,6 +183,34 @@ class VctMixedHoles(C.Structure):     # vct_mixed_holes
         ("count", C.c_void_p),
         ("stats", C.c_void_p),
         ("max_holes", C.c_uint32),
+    ]
+
+
+class VctTemporalParams(C.Structure):    # vct_temporal_params, 12 bytes
+    _fields_ = [
+        ("normal_cos", C.c_float),
+        ("plane_eps", C.c_float),
+        ("max_len", C.c_uint32),
+    ]
+
+
+class VctTemporalArgs(C.Structure):      # vct_temporal_args
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("pos4", C.c_void_p),
+        ("nrm4", C.c_void_p),
+        ("motion4", C.c_void_p),
+        ("prev_cam", C.POINTER(VctCamera)),
+        ("prev_pos4", C.c_void_p),
+        ("prev_nrm4", C.c_void_p),
+        ("n_planes", C.c_uint32),
+        ("cur4", C.c_void_p * 4),
+        ("hist4", C.c_void_p * 4),
+        ("out4", C.c_void_p * 4),
+        ("hist_len", C.c_void_p),
+        ("out_len", C.c_void_p),
+        ("stats", C.c_void_p),
     ]
 
 
@@ -472,6 +504,26 @@ def bind_mixed_extension(lib: C.CDLL, name: str):
     except AttributeError:
         raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
                              "(include/vct_mixed.h is implemented by the HIP library only)") from None
+    fn.restype = res
+    fn.argtypes = args
+    return fn
+
+
+def bind_temporal_extension(lib: C.CDLL, name: str):
+    """The include/vct_temporal.h function `name` of `lib`, with its signature declared;
+    AttributeError (naming the library) if this implementation does not export it."""
+    P, i32 = C.c_void_p, C.c_int32
+    TP = C.POINTER(VctTemporalParams)
+    sig = {
+        "vct_temporal_default_params": (i32, [P, TP]),
+        "vct_temporal_accumulate_device": (i32, [P, C.POINTER(VctTemporalArgs), TP]),
+    }
+    res, args = sig[name]
+    try:
+        fn = getattr(lib, name)
+    except AttributeError:
+        raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
+                             "(include/vct_temporal.h is implemented by the HIP library only)") from None
     fn.restype = res
     fn.argtypes = args
     return fn
