@@ -429,5 +429,6 @@ vct_status vct_dump_info(const char* stem, vct_config* cfg, uint32_t* what);
 #include "vct_mixed.h"      /* mixed-resolution trace (additive; HIP library only) */
 #include "vct_fog.h"        /* volumetric fog (additive; HIP library only) */
 #include "vct_temporal.h"   /* temporal accumulation (additive; HIP library only) */
+#include "vct_sky_view.h"   /* the sky in view: specular cone and background (additive; HIP library only) */
 
 #endif /* VCT_H */

@@ -597,4 +597,43 @@
  *    1 .. VCT_TEMPORAL_MAX_LEN; tan_half finite and > 0, every component of eye', front',
  *    right', up' finite; anything else is VCT_EINVAL with nothing written. */
 
+/* ---- sky in view (vct_sky_specular_device / vct_sky_background_device,
+ *      include/vct_sky_view.h; no new literals; tests/sky_view_ref.py restates it) -------------
+ *  All arithmetic is float32, one rounding per operation, no contraction.  The sky record, its
+ *    input rule, up_n and Sky(d) are those of "sky light"; dot3 is "local lights"'.
+ *  Specular sky, per valid pixel (pos.w != 0, K4's rule) with records P, N, roughness = alb.w:
+ *      o_c = (P_c - g0_c) * inv_h + N_c                           (K4's origin, A.5)
+ *      v_c = eye_c - P_c;  vl = sqrtf((vx*vx + vy*vy) + vz*vz);  v_c = v_c / vl
+ *      ndv = dot3(N, v);  k2 = 2.0f * ndv;  r_c = k2 * N_c - v_c  (A.6's specular cone)
+ *      tau = fminf(fmaxf(roughness, VCT_SPEC_TAU_MIN), VCT_SPEC_TAU_MAX)
+ *      a   = the result of steps 1-5 of "shadow cones" with o, d = r, tau and t_lim = +inf
+ *    (the "light is reached" end never applies).  This is the alpha of K4's own specular cone,
+ *    bit for bit, and the cone takes K4's steps: a call counts exactly the cone steps of K4's
+ *    specular cones on the same frame.
+ *      T   = fmaxf(1.0f - a / VCT_ALPHA_STOP, 0.0f)               (one correctly rounded divide)
+ *      S_c = T * Sky_c(r)                                         (one multiply per channel)
+ *    skyspec4[px] = (S.rgb, T).  A background pixel (pos.w == 0), and every pixel of a context
+ *    with specular = 0, gives +0 in all four channels and counts no step.
+ *    With spec4_inout, at every valid pixel
+ *      spec_c = spec_c + S_c                                      (one add per channel, c = r, g, b)
+ *    and alpha, and every background pixel, untouched.  A specular component that is -0.0f
+ *    becomes +0.0f when S_c is +0 (an all-zero sky changes no other bit).
+ *  Hostile records are legal.  A non-finite r -- a non-finite position or normal, an eye whose
+ *    v.v overflows, or an eye on the pixel itself (vl = 0, v = 0 / 0) -- makes p = o + r t
+ *    fail the inside test of step 1 before the first sample: a = +0, T = 1, no step, and Sky(r)
+ *    is the horizon colour where u is NaN (fmaxf(NaN, 0) is 0), so S is the horizon colour.  A
+ *    NaN roughness clamps to VCT_SPEC_TAU_MIN (fmaxf(NaN, x) is x).  No sample is ever taken
+ *    at a non-finite p.
+ *  Sky background, per pixel with pos.w == 0 (-0.0f is background) of a w x h frame:
+ *      d   = the caster's primary-ray direction of the pixel (vct_view.h pixel_ray with the host
+ *            constants of camera_fields: tan_half = tanf(zoom_deg * 0.5f * 3.14159265358979f /
+ *            180.0f), aspect = (float)w / (float)h; normalised by il = 1.0f / sqrtf(dot3(d, d)),
+ *            d_c * il), as "volumetric fog" reads it for its background rays
+ *      c   = Sky(d)
+ *      linear4[px] = (c.r, c.g, c.b, 1.0f)
+ *      rgba8[px]   = q(tone(c.r)) | q(tone(c.g)) << 8 | q(tone(c.b)) << 16 | 255 << 24
+ *    with tone and q the composite's present step ("volumetric fog", apply).  Alpha 1 marks the
+ *    pixel as shaded: vct_fog_apply_device then takes it through the tone curve, not as a
+ *    clear-colour pixel.  Valid pixels are not read beyond pos.w and not written. */
+
 #endif /* VCT_SPEC_H */

@@ -322,6 +322,7 @@ struct vct_ctx {
     hipStream_t shadow_stream = nullptr;
     int shadow_path = 0;                     // address path of the last march: 32 or 64 (vct_debug_shadow_path)
     int sky_path = 0;                        // the same of the last sky march (vct_debug_sky_path)
+    int sky_view_path = 0;                   // and of the last specular sky march (vct_debug_sky_view_path)
     bool sky_profile = false;                // vct_debug_sky: time the stages of vct_inject_sky with events
     hipEvent_t sky_ev[4] = {};
     float sky_ms[3] = {0, 0, 0};             // march, add and K3 of the last vct_inject_sky

@@ -5,8 +5,8 @@
 //
 //   vct_headless <model.obj> [grid=256] [width=800] [height=600] [frames=5] [out.ppm] [devices=1]
 //                [--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32]
-//                [--light SPEC]... [--shadow-tan T] [--sky Z[:H[:G]]] [--mixed 2|4] [--fog DENSITY]
-//                [--temporal N] [--dynamic FILE.obj [--dynamic-offset x,y,z]]
+//                [--light SPEC]... [--shadow-tan T] [--sky Z[:H[:G]]] [--sky-view] [--mixed 2|4]
+//                [--fog DENSITY] [--temporal N] [--dynamic FILE.obj [--dynamic-offset x,y,z]]
 //   (devices > 1: one process drives that many GPUs through vct_create_multi)
 //   --model: the model matrix of the reference's draw, T(0,-1.75,0) S(0.2)
 //            (r_voxelization.cpp:26-29; default), or none;
@@ -21,6 +21,8 @@
 //   --sky:    a sky (include/vct_sky.h) with up = +y: Z, H and G are the r,g,b of the zenith, the
 //            horizon (default: Z) and the ground (default: 0,0,0).  It is injected per voxel
 //            after the mips and before the bounces, and added per pixel to the diffuse term;
+//   --sky-view: with --sky, the sky in view (include/vct_sky_view.h): the sky is also seen by the
+//            specular cone of every pixel, and the background shows it instead of the clear colour;
 //   --mixed:  2 or 4: the frame is traced at mixed resolution (include/vct_mixed.h): diffuse cones on
 //            a frame that many times smaller per axis, upsampled, holes traced exactly, the
 //            specular cone at full resolution; absent: the full-resolution trace;
@@ -153,7 +155,7 @@ int main(int argc, char** argv) {
     std::string linear;
     std::vector<vct_light> lights;
     float shadow_tan = 0.0f;
-    bool has_sky = false;
+    bool has_sky = false, sky_view = false;
     vct_sky sky{};
     uint32_t mixed = 0;
     float fog_density = 0.0f;
@@ -180,6 +182,7 @@ int main(int argc, char** argv) {
             if (!parse_sky(spec, &sky)) { std::fprintf(stderr, "malformed --sky %s\n", spec.c_str()); return 2; }
             has_sky = true;
         }
+        else if (a == "--sky-view") sky_view = true;
         else if (a == "--mixed" || a.rfind("--mixed=", 0) == 0) {
             const std::string v = a == "--mixed" ? (i + 1 < argc ? argv[++i] : "") : a.substr(8);
             if (v != "2" && v != "4") { std::fprintf(stderr, "malformed --mixed %s (2 or 4)\n", v.c_str()); return 2; }
@@ -217,9 +220,10 @@ int main(int argc, char** argv) {
         else if (a.rfind("--", 0) == 0) { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
         else pos.push_back(a);
     }
+    if (sky_view && !has_sky) { std::fprintf(stderr, "--sky-view needs --sky Z[:H[:G]]\n"); return 2; }
     if (pos.empty()) {
         std::fprintf(stderr, "usage: %s model.obj [grid] [width] [height] [frames] [out.ppm] [devices] "
-                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] [--sky Z[:H[:G]]] [--mixed 2|4] [--fog DENSITY] [--temporal N] "
+                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] [--sky Z[:H[:G]]] [--sky-view] [--mixed 2|4] [--fog DENSITY] [--temporal N] "
                              "[--dynamic FILE.obj [--dynamic-offset x,y,z]] "
                              "[--light dir:d:rgb | point:p:rgb:range | spot:p:d:rgb:range:inner:outer]...\n",
                      argv[0]);
@@ -241,6 +245,7 @@ int main(int argc, char** argv) {
     s.lights = lights;
     s.has_sky = has_sky;
     s.sky = sky;
+    s.sky_view = sky_view;
     s.mixed_factor = mixed;
     s.fog_density = fog_density;
     s.temporal_len = temporal;

@@ -47,6 +47,7 @@ ConeTraceRenderer::~ConeTraceRenderer() {
     vct_device_free(ctx_, counter_);
     if (vis_) vct_device_free(ctx_, vis_);
     if (sky_) vct_device_free(ctx_, sky_);
+    if (sky_spec_) vct_device_free(ctx_, sky_spec_);
     if (fog_) vct_device_free(ctx_, fog_);
     for (void* p : hist_) if (p) vct_device_free(ctx_, p);
     for (void* p : hist_len_) if (p) vct_device_free(ctx_, p);
@@ -197,6 +198,13 @@ void ConeTraceRenderer::Render() {
         check(vct_sky_cones_device(ctx_, a.pos4, a.nrm4, s_.width, s_.height, &s_.sky, (float*)sky_, a.diffuse4, nullptr),
               "vct_sky_cones_device");
     }
+    if (s_.has_sky && s_.sky_view && status_ == VCT_OK) {   // and into the specular plane
+        if (!sky_spec_ && !check(vct_device_alloc(ctx_, (size_t)s_.width * s_.height * 16, &sky_spec_), "alloc specular sky plane"))
+            return;
+        check(vct_sky_specular_device(ctx_, a.pos4, a.nrm4, a.alb4, s_.width, s_.height, a.eye, &s_.sky, (float*)sky_spec_,
+                                      a.spec4, nullptr),
+              "vct_sky_specular_device");
+    }
     if (s_.temporal_len && status_ == VCT_OK) accumulate_diffuse();
 }
 
@@ -250,6 +258,12 @@ vct_status ConeTraceRenderer::composite(float* lin, uint32_t* rgba) {
 }
 
 vct_status ConeTraceRenderer::composite_surface(float* lin, uint32_t* rgba) {
+    const vct_status st = composite_terms(lin, rgba);
+    if (st != VCT_OK || !(s_.has_sky && s_.sky_view)) return st;
+    return vct_sky_background_device(ctx_, &cam_, (const float*)gb_[0], s_.width, s_.height, &s_.sky, lin, rgba);
+}
+
+vct_status ConeTraceRenderer::composite_terms(float* lin, uint32_t* rgba) {
     const float *pos = (const float*)gb_[0], *nrm = (const float*)gb_[1], *alb = (const float*)gb_[2];
     const float* diff = (const float*)(s_.temporal_len && has_prev_ ? hist_[hist_cur_] : out_[0]);   // the accumulated plane
     const float* spec = (const float*)out_[1];

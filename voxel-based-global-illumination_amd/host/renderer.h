@@ -63,6 +63,10 @@ struct ConeTraceSettings {
     // so every composite shows it through albedo x diffuse
     bool has_sky = false;
     vct_sky sky = {{0.0f, 1.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
+    // the sky in view (include/vct_sky_view.h; needs has_sky): the sky is also added to the specular
+    // plane after K4 (vct_sky_specular_device), and every composite is followed by
+    // vct_sky_background_device, so the background shows the sky instead of the clear colour
+    bool sky_view = false;
     // model matrix applied to the model's vertices before K1, column-major; main.cpp
     // sets the reference's T(0,-1.75,0) S(0.2) (r_voxelization.cpp:26-29) by default
     float model[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
@@ -99,7 +103,8 @@ private:
     bool relight();                       // inject -> mips (-> sky, bounces), as after every voxelization
     // row f3 into `lin` (float4) or `rgba` (packed 8-bit), with the light list when there is one
     vct_status composite(float* lin, uint32_t* rgba);
-    vct_status composite_surface(float* lin, uint32_t* rgba);   // the composite without the fog
+    vct_status composite_surface(float* lin, uint32_t* rgba);   // the composite without the fog (with the sky behind it: sky_view)
+    vct_status composite_terms(float* lin, uint32_t* rgba);     // direct + albedo * diffuse + specular by the frame's lights
     std::vector<vct_light> frame_lights() const;                // the light list, or the default light as one
     vct_fog fog() const;                                        // fog_density with the header defaults
 
@@ -112,6 +117,7 @@ private:
     void* vis_ = nullptr;                 // V planes of the soft-shadow composite (shadow_tan > 0), kept
     size_t vis_bytes_ = 0;
     void* sky_ = nullptr;                 // (Sk.rgb, vis) plane of the frame's sky call (has_sky), kept
+    void* sky_spec_ = nullptr;            // (S.rgb, T) plane of the frame's specular sky call (sky_view), kept
     void* fog_ = nullptr;                 // ray, fog and linear planes of the fog pass (fog_density > 0), kept
     vct_camera cam_{};                    // the camera of the last Render(), for the fog's background rays
     // temporal accumulation (temporal_len > 0): the accumulated diffuse planes and history lengths of

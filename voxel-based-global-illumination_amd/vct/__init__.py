@@ -612,6 +612,38 @@ class Context:
             raise VctError(_EINVAL, f"inject_sky: expected a VctSky (vct.sky_light), got {type(sky).__name__}")
         self._check(fn(self.h, C.byref(sky)), "inject_sky")
 
+    # -- the sky in view (include/vct_sky_view.h) ----------------------------
+    def sky_specular_device(self, pos4, nrm4, alb4, width, height, eye, sky, skyspec4, spec4_inout=None,
+                            cone_steps=None):
+        """vct_sky_specular_device: (S.rgb, T) per pixel into skyspec4, a float32 device tensor
+        [height, width, 4]: the sky seen by the pixel's specular cone; spec4_inout (K4's specular
+        plane of the frame): rgb += S.rgb at every valid pixel.  sky: a VctSky (vct.sky_light).
+        cone_steps: a 1-element int64 device tensor that the call adds its cone steps to."""
+        fn = _lib.bind_sky_view_extension(self.lib, "vct_sky_specular_device")
+        if not isinstance(sky, VctSky):
+            raise VctError(_EINVAL, f"sky_specular: expected a VctSky (vct.sky_light), got {type(sky).__name__}")
+        n = 4 * width * height
+        self._check(fn(self.h, *self._gbuf_ptrs(width, height, pos4, nrm4, alb4), width, height, _f3(eye),
+                       C.byref(sky), self._dev(skyspec4, "skyspec4", _F32, n),
+                       self._dev(spec4_inout, "spec4_inout", _F32, n),
+                       self._dev(cone_steps, "cone_steps", _I64, 1)), "sky_specular")
+
+    def sky_background_device(self, cam, pos4, width, height, sky, linear4_inout=None, rgba8_inout=None):
+        """vct_sky_background_device: at every background pixel of a composited frame, the sky
+        colour of the pixel's primary ray through `cam` into the linear frame (alpha 1) and / or
+        its tone-mapped bytes into the RGBA8 frame; valid pixels are untouched."""
+        fn = _lib.bind_sky_view_extension(self.lib, "vct_sky_background_device")
+        if hasattr(cam, "to_ctypes"):
+            cam = cam.to_ctypes()
+        if not isinstance(cam, VctCamera):
+            raise VctError(_EINVAL, f"sky_background: expected a camera, got {type(cam).__name__}")
+        if not isinstance(sky, VctSky):
+            raise VctError(_EINVAL, f"sky_background: expected a VctSky (vct.sky_light), got {type(sky).__name__}")
+        n = 4 * width * height
+        self._check(fn(self.h, C.byref(cam), self._dev(pos4, "pos4", _F32, n), width, height, C.byref(sky),
+                       self._dev(linear4_inout, "linear4_inout", _F32, n),
+                       self._dev(rgba8_inout, "rgba8_inout", _I32, width * height)), "sky_background")
+
     # -- volumetric fog (include/vct_fog.h) ----------------------------------
     def _fog(self, fog, what):
         if not isinstance(fog, VctFog):

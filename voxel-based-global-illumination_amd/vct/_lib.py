@@ -71,6 +71,9 @@ VCT_FOG_DEFAULT_ALBEDO, VCT_FOG_DEFAULT_LEVEL, VCT_FOG_DEFAULT_STEP, VCT_FOG_DEF
 TEMPORAL_EXTENSIONS = ("vct_temporal_default_params", "vct_temporal_accumulate_device")
 VCT_TEMPORAL_DEFAULT_LEN, VCT_TEMPORAL_MAX_LEN = 8, 1024
 
+# include/vct_sky_view.h: the sky in view, likewise HIP only (bind_sky_view_extension)
+SKY_VIEW_EXTENSIONS = ("vct_sky_specular_device", "vct_sky_background_device")
+
 STATUS = {0: "VCT_OK", 1: "VCT_EINVAL", 2: "VCT_ENOMEM", 3: "VCT_EDEVICE", 4: "VCT_ECOMM", 5: "VCT_ESTATE"}
 
 
@@ -465,6 +468,26 @@ def bind_sky_extension(lib: C.CDLL, name: str):
     return fn
 
 
+def bind_sky_view_extension(lib: C.CDLL, name: str):
+    """The include/vct_sky_view.h function `name` of `lib`, with its signature declared;
+    AttributeError (naming the library) if this implementation does not export it."""
+    P, u32, i32 = C.c_void_p, C.c_uint32, C.c_int32
+    F3 = C.POINTER(C.c_float)
+    sig = {
+        "vct_sky_specular_device": (i32, [P, P, P, P, u32, u32, F3, C.POINTER(VctSky), P, P, P]),
+        "vct_sky_background_device": (i32, [P, C.POINTER(VctCamera), P, u32, u32, C.POINTER(VctSky), P, P]),
+    }
+    res, args = sig[name]
+    try:
+        fn = getattr(lib, name)
+    except AttributeError:
+        raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
+                             "(include/vct_sky_view.h is implemented by the HIP library only)") from None
+    fn.restype = res
+    fn.argtypes = args
+    return fn
+
+
 def bind_dynamic_extension(lib: C.CDLL, name: str):
     """The include/vct_dynamic.h function `name` of `lib`, with its signature declared;
     AttributeError (naming the library) if this implementation does not export it."""
@@ -555,6 +578,25 @@ def debug_sky_path(lib: C.CDLL, handle) -> int:
     """Test hook (vct_debug_sky_path): the address path the context's last sky march was
     launched with -- 32 (buffer resources), 64 (64-bit addresses), 0 before any."""
     fn = lib.vct_debug_sky_path
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p]
+    return int(fn(handle))
+
+
+def debug_sky_view(lib: C.CDLL, force64: int = -1) -> None:
+    """Test and tool hook (vct_debug_sky_view, not part of the headers).  force64 >= 0,
+    process-wide: nonzero sends every grid's specular sky march through the 64-bit-address path
+    (the one 1024^3 takes)."""
+    fn = lib.vct_debug_sky_view
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int]
+    fn(int(force64))
+
+
+def debug_sky_view_path(lib: C.CDLL, handle) -> int:
+    """Test hook (vct_debug_sky_view_path): the address path the context's last specular sky
+    march was launched with -- 32 (buffer resources), 64 (64-bit addresses), 0 before any."""
+    fn = lib.vct_debug_sky_view_path
     fn.restype = C.c_int
     fn.argtypes = [C.c_void_p]
     return int(fn(handle))
