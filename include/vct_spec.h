@@ -32,6 +32,7 @@
 #define VCT_SQRT3           1.7320508f   /* t_max = n * sqrt(3) (voxel units)       */
 #define VCT_SPEC_TAU_MIN    0.02f        /* specular tau = clamp(roughness, .02, 1) */
 #define VCT_SPEC_TAU_MAX    1.0f
+#define VCT_QUERY_MAX_STEPS 4096        /* loop bound of a cone query (> 2*1024*sqrt(3) + 1) */
 
 /* ---- log2 used for the mip level m = log2(D) (D >= 1) ----------------------
  * m = e + 2*s*P(s^2)/ln2 with x = 2^e * f, f in [1/sqrt2, sqrt2], s=(f-1)/(f+1)
@@ -635,5 +636,71 @@
  *    with tone and q the composite's present step ("volumetric fog", apply).  Alpha 1 marks the
  *    pixel as shaded: vct_fog_apply_device then takes it through the tone curve, not as a
  *    clear-colour pixel.  Valid pixels are not read beyond pos.w and not written. */
+
+/* ---- cone queries (vct_cone_query_device, include/vct_query.h; tests/query_ref.py restates
+ *      it) ------------------------------------------------------------------------------------
+ *  All arithmetic is float32, one rounding per operation, no contraction; the fused operations
+ *    are the fmaf() calls named here.  A cone is the record (p, tau, d, t_lim, off, valid).
+ *  valid == 0 (-0.0f too): out4 = +0 in all four channels, steps = 0; nothing is marched.  A
+ *    NaN valid is not 0.
+ *  Origin, per component:  o_c = ((p_c - g0_c) * inv_h) + off_c   (K4's origin, A.5, with off in
+ *    the place of the normal).
+ *  Direction: d as given, never normalised.  Faces f_c from d_c >= 0.0f (a NaN or -0 component
+ *    selects the negative face, as in K4), face weights wd_c = d_c * d_c.
+ *  Aperture: tau' = fminf(fmaxf(tau, VCT_SPEC_TAU_MIN), VCT_SPEC_TAU_MAX) (a NaN tau clamps to
+ *    VCT_SPEC_TAU_MIN), tau2 = 2.0f * tau'.
+ *  March (A.6, K4's): c = (0, 0, 0), a = 0, t = 1.0f, steps = 0; repeat at most
+ *    VCT_QUERY_MAX_STEPS times:
+ *      1. stop unless a < VCT_ALPHA_STOP;  stop unless t <= t_max = (float)n * VCT_SQRT3;
+ *         stop if t >= t_lim (false for a NaN t_lim, which therefore never limits; t_lim <= 1
+ *         gives zero steps);  q_c = o_c + d_c * t;  stop unless 0 <= q_c <= (float)n for every c
+ *         (a NaN fails)
+ *      2. D = fmaxf(1.0f, tau2 * t);  m = fminf(log2(D), (float)L) with the log2 above;
+ *         l0 = (int)m;  fr = m - (float)l0
+ *      3. s = S_l0(q);  if fr > 0 and l0 < L:  s1 = S_(l0+1)(q) and per channel
+ *         s = fmaf(fr, s1, (1.0f - fr) * s)
+ *      4. oma = 1.0f - a;  c = fmaf(oma, s.rgb, c);  a = fmaf(oma, s.a, a)   (a from the old oma)
+ *      5. t = t + VCT_STEP_SCALE * D;  steps += 1
+ *    The level sample S_l(q), four channels: u_c = q_c * 2^-l - 0.5f, i_c = floorf(u_c),
+ *    w1_c = u_c - i_c, w0_c = 1.0f - w1_c; the eight corner texels i + (dx, dy, dz) in the order
+ *    dz, dy, dx (dx fastest), each with wc = (wx * wy) * wz; a corner outside the level adds
+ *    nothing; per channel acc = fmaf(wc, v, acc) from acc = +0, where v is the texel (level 0,
+ *    or an isotropic pyramid) or, on an anisotropic level l > 0,
+ *      v = fmaf(wd_z, T_fz, fmaf(wd_y, T_fy, wd_x * T_fx))
+ *    of the corner's texels in the three selected faces.
+ *    t grows by at least 0.5 a step, so a cone takes fewer than 2 n sqrt(3) + 1 steps; the
+ *    integer cap is above that for n <= 1024 and is never reached by legal arithmetic.  It
+ *    bounds the loop in the kernel and in the reference alike.
+ *  out4 = (c.rgb, a): the layout of K4's spec4.  No sample is ever taken at a non-finite q.
+ *  Identities (bit for bit): p = P, off = N, d = "sky in view"'s r, tau = alb.w, t_lim = +inf is
+ *    the pixel's spec4, with the steps of K4's specular cone; the rows (cn, ct, cb, w) of the
+ *    context's diffuse set with d_k = (cn * N + ct * T) + cb * B, tau = VCT_TAN30 (VCT_TAN20 for
+ *    16), accumulated in row order as irr = fmaf(w, c_k, irr), occ = fmaf(w, a_k, occ), are
+ *    diffuse4 = (irr, 1.0f - occ). */
+
+/* ---- probe grid (vct_probe_build_device / vct_probe_sample_device, include/vct_query.h) ------
+ *  Input rule: origin finite, spacing finite and > 0, each dim in 1 .. VCT_PROBE_MAX_DIM (256,
+ *    include/vct_query.h).
+ *  Build.  Probe (i, j, k), stored at [k][j][i], stands at P_c = fmaf((float)i_c, spacing,
+ *    origin_c).  Face f (VCT_FACE_* order) = the out4 of the cone query p = P, off = +0,
+ *    d = the unit axis of f (the other two components +0), tau = VCT_SPEC_TAU_MAX,
+ *    t_lim = +inf, valid = 1.  With o the cone's origin (above; the same for the six faces),
+ *    state = 1 when 0 <= o_c < (float)n for every c and K1's occupancy of the voxel
+ *    floorf(o) is 0; otherwise (a wall, outside the grid, an overflowed P) state = 0.
+ *  Sample, per point with pos.w != 0, per axis c with D_c = dims_c:
+ *      g = (P_c - origin_c) / spacing                     (one correctly rounded division)
+ *      g = fminf(fmaxf(g, 0.0f), (float)(D_c - 1))        (a NaN becomes 0)
+ *      i0 = D_c == 1 ? 0 : min((int)floorf(g), D_c - 2);  fr = g - (float)i0
+ *      w_c[0] = 1.0f - fr,  w_c[1] = fr
+ *    The eight corners in the order cn = dx + 2 dy + 4 dz, wc = (wx[dx] * wy[dy]) * wz[dz].  A
+ *    corner with i0 + d >= D_c on some axis (only when D_c == 1), or whose state is 0, is left
+ *    out.  Over the kept corners, in order: W = W + wc from +0, and for each of the three
+ *    faces the normal selects (f_c from n_c >= 0.0f, as a cone's) and each channel
+ *      S_f = fmaf(wc, probe[f], S_f)                      from +0
+ *    Then with wn_c = n_c * n_c (the normal as given)
+ *      V = fmaf(wn_z, S_fz, fmaf(wn_y, S_fy, wn_x * S_fx))       per channel
+ *    W > 0:  out4 = (V.r / W, V.g / W, V.b / W, 1.0f - V.a / W);  otherwise (W = 0, or a NaN)
+ *    out4 = (+0, +0, +0, 1.0f) and the point is a miss.  A background point (pos.w == 0, -0 too)
+ *    gets +0 in all four channels and is no miss. */
 
 #endif /* VCT_SPEC_H */

@@ -6,7 +6,7 @@
 //   vct_headless <model.obj> [grid=256] [width=800] [height=600] [frames=5] [out.ppm] [devices=1]
 //                [--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32]
 //                [--light SPEC]... [--shadow-tan T] [--sky Z[:H[:G]]] [--sky-view] [--mixed 2|4]
-//                [--fog DENSITY] [--temporal N] [--dynamic FILE.obj [--dynamic-offset x,y,z]]
+//                [--fog DENSITY] [--temporal N] [--probes D] [--dynamic FILE.obj [--dynamic-offset x,y,z]]
 //   (devices > 1: one process drives that many GPUs through vct_create_multi)
 //   --model: the model matrix of the reference's draw, T(0,-1.75,0) S(0.2)
 //            (r_voxelization.cpp:26-29; default), or none;
@@ -33,6 +33,9 @@
 //            diffuse plane with the reprojected history of the frame before it, a running mean of at
 //            most N frames, the other parameters at the header's defaults, and the composite reads
 //            the accumulated plane; absent: every frame stands alone;
+//   --probes: D in 1 .. 256: a D^3 grid of ambient-cube probes (include/vct_query.h) over the grid's
+//            AABB, built after every relight; the composite reads the probe-sampled plane in place of
+//            K4's diffuse plane (the specular cone is still traced); absent: K4's diffuse plane;
 //   --dynamic: a second model, voxelized as the context's dynamic layer (include/vct_dynamic.h)
 //            on top of the first one's grid; Kd materials only (its diffuse maps are not loaded).
 //            --dynamic-offset: a world-space translation applied after the model matrix of
@@ -160,6 +163,7 @@ int main(int argc, char** argv) {
     uint32_t mixed = 0;
     float fog_density = 0.0f;
     uint32_t temporal = 0;
+    uint32_t probes = 0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--model=reference") ref_model = true;
@@ -207,6 +211,16 @@ int main(int argc, char** argv) {
             }
             temporal = (uint32_t)t;
         }
+        else if (a == "--probes" || a.rfind("--probes=", 0) == 0) {
+            const std::string v = a == "--probes" ? (i + 1 < argc ? argv[++i] : "") : a.substr(9);
+            char* end = nullptr;
+            const long d = std::strtol(v.c_str(), &end, 10);
+            if (v.empty() || v[0] < '0' || v[0] > '9' || *end || d < 1 || d > (long)VCT_PROBE_MAX_DIM) {
+                std::fprintf(stderr, "malformed --probes %s (1 .. %d)\n", v.c_str(), VCT_PROBE_MAX_DIM);
+                return 2;
+            }
+            probes = (uint32_t)d;
+        }
         else if (a == "--dynamic-offset" || a.rfind("--dynamic-offset=", 0) == 0) {
             const std::string spec = a == "--dynamic-offset" ? (i + 1 < argc ? argv[++i] : "") : a.substr(17);
             if (!parse_offset(spec, dyn_offset)) { std::fprintf(stderr, "malformed --dynamic-offset %s\n", spec.c_str()); return 2; }
@@ -223,7 +237,7 @@ int main(int argc, char** argv) {
     if (sky_view && !has_sky) { std::fprintf(stderr, "--sky-view needs --sky Z[:H[:G]]\n"); return 2; }
     if (pos.empty()) {
         std::fprintf(stderr, "usage: %s model.obj [grid] [width] [height] [frames] [out.ppm] [devices] "
-                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] [--sky Z[:H[:G]]] [--sky-view] [--mixed 2|4] [--fog DENSITY] [--temporal N] "
+                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] [--sky Z[:H[:G]]] [--sky-view] [--mixed 2|4] [--fog DENSITY] [--temporal N] [--probes D] "
                              "[--dynamic FILE.obj [--dynamic-offset x,y,z]] "
                              "[--light dir:d:rgb | point:p:rgb:range | spot:p:d:rgb:range:inner:outer]...\n",
                      argv[0]);
@@ -249,6 +263,7 @@ int main(int argc, char** argv) {
     s.mixed_factor = mixed;
     s.fog_density = fog_density;
     s.temporal_len = temporal;
+    s.probes = probes;
     if (ref_model) ReferenceModelMatrix(s.model);
 
     AssetsManager& A = AssetsManager::Instance();            // assets.cpp:22-45

@@ -49,6 +49,7 @@ ConeTraceRenderer::~ConeTraceRenderer() {
     if (sky_) vct_device_free(ctx_, sky_);
     if (sky_spec_) vct_device_free(ctx_, sky_spec_);
     if (fog_) vct_device_free(ctx_, fog_);
+    for (void* p : {probes_, probe_state_, probe_plane_}) if (p) vct_device_free(ctx_, p);
     for (void* p : hist_) if (p) vct_device_free(ctx_, p);
     for (void* p : hist_len_) if (p) vct_device_free(ctx_, p);
     for (void* p : prev_gb_) if (p) vct_device_free(ctx_, p);
@@ -128,7 +129,25 @@ bool ConeTraceRenderer::relight() {
         if (!check(vct_build_fog(ctx_, &f, lights.data(), (uint32_t)lights.size(), tan_half.data()), "vct_build_fog"))
             return false;
     }
+    if (s_.probes) {   // the probes see the finished pyramid: sky and bounces included
+        const size_t n = (size_t)s_.probes * s_.probes * s_.probes;
+        if (!probes_ && !check(vct_device_alloc(ctx_, n * 6 * 16, &probes_), "alloc probes")) return false;
+        if (!probe_state_ && !check(vct_device_alloc(ctx_, n * 4, &probe_state_), "alloc probe states")) return false;
+        const vct_probe_grid pg = probe_grid();
+        if (!check(vct_probe_build_device(ctx_, &pg, (float*)probes_, (uint32_t*)probe_state_, nullptr), "vct_probe_build_device"))
+            return false;
+    }
     return true;
+}
+
+vct_probe_grid ConeTraceRenderer::probe_grid() const {
+    vct_probe_grid pg{};
+    pg.spacing = s_.extent / (float)s_.probes;
+    for (int k = 0; k < 3; ++k) {
+        pg.origin[k] = s_.aabb_min[k] + 0.5f * pg.spacing;
+        pg.dims[k] = s_.probes;
+    }
+    return pg;
 }
 
 std::vector<vct_light> ConeTraceRenderer::frame_lights() const {
@@ -267,6 +286,17 @@ vct_status ConeTraceRenderer::composite_terms(float* lin, uint32_t* rgba) {
     const float *pos = (const float*)gb_[0], *nrm = (const float*)gb_[1], *alb = (const float*)gb_[2];
     const float* diff = (const float*)(s_.temporal_len && has_prev_ ? hist_[hist_cur_] : out_[0]);   // the accumulated plane
     const float* spec = (const float*)out_[1];
+    if (s_.probes) {   // the probe grid lights the frame in place of K4's diffuse cones
+        if (!probe_plane_) {
+            const vct_status st = vct_device_alloc(ctx_, (size_t)s_.width * s_.height * 16, &probe_plane_);
+            if (st != VCT_OK) return st;
+        }
+        const vct_probe_grid pg = probe_grid();
+        const vct_status st = vct_probe_sample_device(ctx_, &pg, (const float*)probes_, (const uint32_t*)probe_state_, pos, nrm,
+                                                      s_.width * s_.height, (float*)probe_plane_, nullptr);
+        if (st != VCT_OK) return st;
+        diff = (const float*)probe_plane_;
+    }
     if (s_.shadow_tan > 0.0f) {   // soft shadows: V per (light, pixel) from shadow cones, then the composite over it
         const std::vector<vct_light> lights = frame_lights();
         const std::vector<float> tan_half(lights.size(), s_.shadow_tan);

@@ -58,6 +58,11 @@ struct ConeTraceSettings {
     // diffuse plane with the reprojected history of the previous Render(), and the composite
     // reads the accumulated plane; 0: every frame stands alone
     uint32_t temporal_len = 0;
+    // > 0: a probes^3 grid of ambient-cube probes (include/vct_query.h; 1 .. VCT_PROBE_MAX_DIM) over
+    // the grid's AABB, the first and last probe half a spacing inside it: built at the end of every
+    // relight, sampled at the frame's G-buffer by every composite, which then reads that plane in
+    // place of K4's diffuse plane (and of the accumulated one); 0: K4's diffuse plane
+    uint32_t probes = 0;
     // a sky (include/vct_sky.h): injected per voxel after the mips and before the bounces
     // (vct_inject_sky), and added per pixel to the diffuse plane after K4 (vct_sky_cones_device),
     // so every composite shows it through albedo x diffuse
@@ -107,6 +112,7 @@ private:
     vct_status composite_terms(float* lin, uint32_t* rgba);     // direct + albedo * diffuse + specular by the frame's lights
     std::vector<vct_light> frame_lights() const;                // the light list, or the default light as one
     vct_fog fog() const;                                        // fog_density with the header defaults
+    vct_probe_grid probe_grid() const;                          // the probes^3 grid over the AABB
 
     std::string model_name_;
     ConeTraceSettings s_;
@@ -118,6 +124,9 @@ private:
     size_t vis_bytes_ = 0;
     void* sky_ = nullptr;                 // (Sk.rgb, vis) plane of the frame's sky call (has_sky), kept
     void* sky_spec_ = nullptr;            // (S.rgb, T) plane of the frame's specular sky call (sky_view), kept
+    void* probes_ = nullptr;              // probes, states and the sampled plane of the probe grid (probes > 0), kept
+    void* probe_state_ = nullptr;
+    void* probe_plane_ = nullptr;
     void* fog_ = nullptr;                 // ray, fog and linear planes of the fog pass (fog_density > 0), kept
     vct_camera cam_{};                    // the camera of the last Render(), for the fog's background rays
     // temporal accumulation (temporal_len > 0): the accumulated diffuse planes and history lengths of

@@ -32,10 +32,11 @@ from ._lib import VCT_ALL_RANKS, VctCamera, VctCommId, VctConfig, VctLight, VctS
 from ._lib import VCT_CONES_DIFFUSE, VCT_CONES_SPECULAR, VctMixedHoles, VctMixedParams
 from ._lib import VctFog
 from ._lib import VctTemporalArgs, VctTemporalParams
+from ._lib import VctCone, VctConeQueryArgs, VctProbeGrid
 
 __all__ = ["VctTemporalParams","Context", "VctError", "VctConfig", "VctCamera", "tiles_for_rank", "tile_offset", "VERTEX_FLOATS",
            "VCT_ALL_RANKS", "comm_frame_layout", "VctLight", "directional_light", "point_light", "spot_light",
-           "VctSky", "sky_light", "VctFog", "fog", "VctMixedParams", "VctMixedHoles", "VCT_CONES_DIFFUSE", "VCT_CONES_SPECULAR"]
+           "VctSky", "sky_light", "VctFog", "fog", "VctCone", "VctProbeGrid", "probe_grid", "VctMixedParams", "VctMixedHoles", "VCT_CONES_DIFFUSE", "VCT_CONES_SPECULAR"]
 
 VERTEX_FLOATS = 14          # reference Vertex: Position, Normal, TexCoords, Tangent, Bitangent
 VERTEX_STRIDE = VERTEX_FLOATS * 4
@@ -105,6 +106,15 @@ def fog(density, albedo=(_lib.VCT_FOG_DEFAULT_ALBEDO,) * 3, ambient=0.0, level=_
     f = VctFog()
     f.density, f.albedo, f.ambient, f.level, f.step = float(density), _f3(albedo), float(ambient), int(level), float(step)
     return f
+
+
+def probe_grid(origin, spacing, dims) -> VctProbeGrid:
+    """A vct_probe_grid: probe (i, j, k) at origin + (i, j, k) * spacing, dims = (dx, dy, dz).  The
+    library checks the record's input rule when a call uses it."""
+    g = VctProbeGrid()
+    g.origin, g.spacing = _f3(origin), float(spacing)
+    g.dims = (C.c_uint32 * 3)(*[int(v) for v in dims])
+    return g
 
 
 def _light_array(lights):
@@ -643,6 +653,49 @@ class Context:
         self._check(fn(self.h, C.byref(cam), self._dev(pos4, "pos4", _F32, n), width, height, C.byref(sky),
                        self._dev(linear4_inout, "linear4_inout", _F32, n),
                        self._dev(rgba8_inout, "rgba8_inout", _I32, width * height)), "sky_background")
+
+    # -- cone queries and the probe grid (include/vct_query.h) ---------------
+    def cone_query_device(self, cones, count, out4, steps=None, cone_steps=None):
+        """vct_cone_query_device: marches `count` vct_cone records -- `cones`, a float32 device
+        tensor [count, 12] (p, tau, d, t_lim, off, valid) -- and writes (c.rgb, a) per cone into
+        out4, a float32 device tensor [count, 4].  steps: an int32 device tensor [count] that
+        receives the steps per cone; cone_steps: a 1-element int64 device tensor that the call
+        adds its steps to.  Order the cones spatially: the call does not sort."""
+        fn = _lib.bind_query_extension(self.lib, "vct_cone_query_device")
+        a = _lib.VctConeQueryArgs()
+        a.cones = self._dev(cones, "cones", _F32, 12 * count)
+        a.count = int(count)
+        a.out4 = self._dev(out4, "out4", _F32, 4 * count)
+        a.steps = self._dev(steps, "steps", _I32, count)
+        a.cone_steps = self._dev(cone_steps, "cone_steps", _I64, 1)
+        self._check(fn(self.h, C.byref(a)), "cone_query")
+
+    @staticmethod
+    def _probe_grid(grid, what):
+        if not isinstance(grid, _lib.VctProbeGrid):
+            raise VctError(_EINVAL, f"{what}: expected a VctProbeGrid (vct.probe_grid), got {type(grid).__name__}")
+        return int(grid.dims[0]) * int(grid.dims[1]) * int(grid.dims[2])
+
+    def probe_build_device(self, grid, probes, state, cone_steps=None):
+        """vct_probe_build_device: the six axis cones of every probe of `grid` (a VctProbeGrid)
+        into probes, a float32 device tensor [dz, dy, dx, 6, 4], and the probes' validity into
+        state, an int32 device tensor [dz, dy, dx]."""
+        fn = _lib.bind_query_extension(self.lib, "vct_probe_build_device")
+        n = self._probe_grid(grid, "probe_build")
+        self._check(fn(self.h, C.byref(grid), self._dev(probes, "probes", _F32, 24 * n),
+                       self._dev(state, "state", _I32, n), self._dev(cone_steps, "cone_steps", _I64, 1)), "probe_build")
+
+    def probe_sample_device(self, grid, probes, state, pos4, nrm4, count, out4, misses=None):
+        """vct_probe_sample_device: the probes around each of `count` points (pos4, nrm4: float32
+        device tensors [count, 4]) blended into out4 [count, 4], a plane with the meaning of
+        K4's diffuse4.  misses: a 1-element int32 device tensor, += the points without a valid
+        probe around them."""
+        fn = _lib.bind_query_extension(self.lib, "vct_probe_sample_device")
+        n = self._probe_grid(grid, "probe_sample")
+        self._check(fn(self.h, C.byref(grid), self._dev(probes, "probes", _F32, 24 * n),
+                       self._dev(state, "state", _I32, n), self._dev(pos4, "pos4", _F32, 4 * count),
+                       self._dev(nrm4, "nrm4", _F32, 4 * count), int(count), self._dev(out4, "out4", _F32, 4 * count),
+                       self._dev(misses, "misses", _I32, 1)), "probe_sample")
 
     # -- volumetric fog (include/vct_fog.h) ----------------------------------
     def _fog(self, fog, what):

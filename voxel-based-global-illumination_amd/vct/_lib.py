@@ -74,6 +74,10 @@ VCT_TEMPORAL_DEFAULT_LEN, VCT_TEMPORAL_MAX_LEN = 8, 1024
 # include/vct_sky_view.h: the sky in view, likewise HIP only (bind_sky_view_extension)
 SKY_VIEW_EXTENSIONS = ("vct_sky_specular_device", "vct_sky_background_device")
 
+# include/vct_query.h: cone queries and the probe grid, likewise HIP only (bind_query_extension)
+QUERY_EXTENSIONS = ("vct_cone_query_device", "vct_probe_build_device", "vct_probe_sample_device")
+VCT_QUERY_MAX_STEPS, VCT_PROBE_MAX_DIM = 4096, 256
+
 STATUS = {0: "VCT_OK", 1: "VCT_EINVAL", 2: "VCT_ENOMEM", 3: "VCT_EDEVICE", 4: "VCT_ECOMM", 5: "VCT_ESTATE"}
 
 
@@ -214,6 +218,35 @@ class VctTemporalArgs(C.Structure):      # vct_temporal_args
         ("hist_len", C.c_void_p),
         ("out_len", C.c_void_p),
         ("stats", C.c_void_p),
+    ]
+
+
+class VctCone(C.Structure):              # vct_cone, 48 bytes
+    _fields_ = [
+        ("p", C.c_float * 3),
+        ("tau", C.c_float),
+        ("d", C.c_float * 3),
+        ("t_lim", C.c_float),
+        ("off", C.c_float * 3),
+        ("valid", C.c_float),
+    ]
+
+
+class VctConeQueryArgs(C.Structure):     # vct_cone_query_args
+    _fields_ = [
+        ("cones", C.c_void_p),
+        ("count", C.c_uint32),
+        ("out4", C.c_void_p),
+        ("steps", C.c_void_p),
+        ("cone_steps", C.c_void_p),
+    ]
+
+
+class VctProbeGrid(C.Structure):         # vct_probe_grid, 28 bytes
+    _fields_ = [
+        ("origin", C.c_float * 3),
+        ("spacing", C.c_float),
+        ("dims", C.c_uint32 * 3),
     ]
 
 
@@ -483,6 +516,27 @@ def bind_sky_view_extension(lib: C.CDLL, name: str):
     except AttributeError:
         raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
                              "(include/vct_sky_view.h is implemented by the HIP library only)") from None
+    fn.restype = res
+    fn.argtypes = args
+    return fn
+
+
+def bind_query_extension(lib: C.CDLL, name: str):
+    """The include/vct_query.h function `name` of `lib`, with its signature declared;
+    AttributeError (naming the library) if this implementation does not export it."""
+    P, u32, i32 = C.c_void_p, C.c_uint32, C.c_int32
+    PG = C.POINTER(VctProbeGrid)
+    sig = {
+        "vct_cone_query_device": (i32, [P, C.POINTER(VctConeQueryArgs)]),
+        "vct_probe_build_device": (i32, [P, PG, P, P, P]),
+        "vct_probe_sample_device": (i32, [P, PG, P, P, P, P, u32, P, P]),
+    }
+    res, args = sig[name]
+    try:
+        fn = getattr(lib, name)
+    except AttributeError:
+        raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
+                             "(include/vct_query.h is implemented by the HIP library only)") from None
     fn.restype = res
     fn.argtypes = args
     return fn
