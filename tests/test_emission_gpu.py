@@ -330,6 +330,49 @@ def test_composite_small_and_hostile_frames(gpu_ready, oracle_mod):
     ctx.close()
 
 
+def test_composite_identities_on_a_partial_block(gpu_ready, oracle_mod):
+    """The three light-list composites are one kernel: with scale +0 the emissive one equals
+    vct_composite_lights_device (vis NULL) and vct_composite_shadowed_device (vis V), bit for bit in
+    both outputs.  n = 16, a 13 x 7 frame (91 lanes of one 256-lane block) with background pixels
+    and one non-finite position, one directional, one point and one spot light.  test_composite has
+    the first identity on a clean 80 x 48 frame and the second through the reference, linear only."""
+    import torch
+    n, w, h = 16, 13, 7
+    L = R.lamp(n)
+    S7 = lights_ref.light_set_s(n)
+    lights = [next(l for l in S7 if l.type == t) for t in (0, 1, 2)]
+    ctx = _lamp_ctx(n)
+    assert ctx.emission_voxels() > 0                                       # a live grid: only scale +0 switches the term off
+    ctx.inject_lights(lights)
+    ctx.build_mips()
+    gb, D, S = _frame(ctx, w, h)
+    vis = torch.full((len(lights), h, w), float("nan"), device="cuda")
+    ctx.shadow_cones_device(gb[0], gb[1], w, h, lights, [0.1, 0.0, 0.2], vis)   # V of the clean frame
+    torch.cuda.synchronize()
+    pos = gb[0].cpu().numpy()
+    pos[0, :3, 3] = 0.0                                                    # background, whatever the rays met
+    fg = np.argwhere(pos[..., 3] != 0)
+    assert len(fg) >= 20 and (pos[..., 3] == 0).sum() >= 3
+    pos[fg[7][0], fg[7][1], 0] = np.nan
+    gb[0] = torch.from_numpy(pos).cuda()
+
+    def other(call, *tail):
+        lin = torch.full((h, w, 4), float("nan"), device="cuda")
+        px = torch.zeros((h, w), dtype=torch.int32, device="cuda")
+        call(*gb, D, S, w, h, lights, *tail, out_linear4=lin, out_rgba8=px)
+        torch.cuda.synchronize()
+        return lin.cpu().numpy(), px.cpu().numpy().view(np.uint32)
+
+    lin, px = _emissive(ctx, gb, D, S, lights, None, 0.0)
+    want, want_px = other(ctx.composite_lights_device)
+    assert bits_equal(lin, want) and np.array_equal(px, want_px)
+    lin, px = _emissive(ctx, gb, D, S, lights, vis, 0.0)
+    soft, soft_px = other(ctx.composite_shadowed_device, vis)
+    assert bits_equal(lin, soft) and np.array_equal(px, soft_px)
+    assert not bits_equal(soft, want)                                      # V is not the walk's
+    ctx.close()
+
+
 # ---- 7. state and errors -----------------------------------------------------------------
 def test_errors_and_state(gpu_ready, oracle_mod, tmp_path):
     import torch

@@ -49,11 +49,6 @@ vct_status use_device(vct_ctx* c) {
     return VCT_OK;
 }
 
-struct DeviceBuf {  // RAII for per-call uploads
-    void* p = nullptr;
-    ~DeviceBuf() { if (p) (void)hipFree(p); }
-};
-
 }  // namespace
 
 namespace vct {
@@ -473,37 +468,23 @@ static vct_status voxelize_host(vct_ctx* c, const void* verts, uint32_t stride, 
     // the Kd rule (vct_spec.h "K1 input rule"), on the host before any launch: the Kd of every
     // material a triangle uses (an out-of-range material index is K1's to report).  The
     // previous grid is refused from here on, as after a failed K1
-    if (kd4)
-        for (uint32_t t = 0; t < n_tri; ++t) {
-            const uint32_t m = tri_mat ? tri_mat[t] : 0u;
-            if (m >= n_mat) continue;
-            const float* k = kd4 + 4 * (size_t)m;
-            if (!(fabsf(k[0]) < VCT_KD_LIMIT && fabsf(k[1]) < VCT_KD_LIMIT && fabsf(k[2]) < VCT_KD_LIMIT)) {
-                Grid& g = c->grid;
-                g.voxelized = g.injected = g.mipped = g.bounced = g.emitted = g.skied = false;
-                g.k2_coarse_ok = g.k3_sparse_ok = g.zm_valid = false;
-                g.k3_live_bz = 0;
-                ++c->grid_epoch;
-                return fail(c, VCT_EINVAL, kKdMessage);
-            }
-        }
+    if (!used_kd_legal(tri_mat, n_tri, kd4, n_mat)) {
+        Grid& g = c->grid;
+        g.voxelized = g.injected = g.mipped = g.bounced = g.emitted = g.skied = false;
+        g.k2_coarse_ok = g.k3_sparse_ok = g.zm_valid = false;
+        g.k3_live_bz = 0;
+        ++c->grid_epoch;
+        return fail(c, VCT_EINVAL, kKdMessage);
+    }
     // host -> device staging (the reference keeps CPU copies of vertices / indices
     // next to its GL buffers, mesh.h:17-18; this is the same one-time upload)
-    DeviceBuf dv, di, dm, dk, dmap, derr;
-    const size_t vbytes = (size_t)stride * n_verts;
-    if (vbytes) VCT_HIP(hipMalloc(&dv.p, vbytes), "hipMalloc verts");
-    if (n_idx) VCT_HIP(hipMalloc(&di.p, (size_t)n_idx * 4), "hipMalloc idx");
-    if (tri_mat && n_tri) VCT_HIP(hipMalloc(&dm.p, (size_t)n_tri * 4), "hipMalloc mat");
-    if (kd4) VCT_HIP(hipMalloc(&dk.p, (size_t)n_mat * 16), "hipMalloc kd");
-    if (map) VCT_HIP(hipMalloc(&dmap.p, (size_t)n_mat * 4), "hipMalloc map");
-    VCT_HIP(hipMalloc(&derr.p, 4), "hipMalloc err");
-    if (vbytes) VCT_HIP(hipMemcpyAsync(dv.p, verts, vbytes, hipMemcpyHostToDevice, c->stream), "upload verts");
-    if (n_idx) VCT_HIP(hipMemcpyAsync(di.p, idx, (size_t)n_idx * 4, hipMemcpyHostToDevice, c->stream), "upload idx");
-    if (dm.p) VCT_HIP(hipMemcpyAsync(dm.p, tri_mat, (size_t)n_tri * 4, hipMemcpyHostToDevice, c->stream), "upload mat");
-    if (dk.p) VCT_HIP(hipMemcpyAsync(dk.p, kd4, (size_t)n_mat * 16, hipMemcpyHostToDevice, c->stream), "upload kd");
-    if (dmap.p) VCT_HIP(hipMemcpyAsync(dmap.p, map, (size_t)n_mat * 4, hipMemcpyHostToDevice, c->stream), "upload map");
-    return voxelize_dev(c, dv.p, stride, n_verts, (const uint32_t*)di.p, n_tri, (const uint32_t*)dm.p,
-                        (const float4*)dk.p, n_mat, (const int32_t*)dmap.p, uv_offset, (int*)derr.p);
+    MeshStage ms;
+    DevTmp derr;
+    VCT_HIP(hipMalloc(&derr.p, 4), "hipMalloc err");   // before the uploads are queued
+    if ((st = stage_mesh(c, ms, verts, (size_t)stride * n_verts, idx, n_idx, tri_mat, kd4, "kd", map, n_mat)) != VCT_OK)
+        return st;
+    return voxelize_dev(c, ms.verts.p, stride, n_verts, (const uint32_t*)ms.idx.p, n_tri, (const uint32_t*)ms.mat.p,
+                        (const float4*)ms.mats.p, n_mat, (const int32_t*)ms.map.p, uv_offset, (int*)derr.p);
 }
 
 static vct_status voxelize_device(vct_ctx* c, const void* verts, uint32_t stride, uint32_t n_verts,

@@ -82,6 +82,13 @@ __device__ __forceinline__ bool occ_at(const unsigned long long* __restrict__ bi
     return (bits[v >> 6] >> (v & 63)) & 1ull;
 }
 
+// set bits of `word` below bit b, plus the word's prefix: the rank of voxel v = 64 w + b among a
+// bit mask's set bits (the emission grid's lookups, Emission in vct_internal.h)
+__device__ __forceinline__ uint32_t bit_rank(const uint32_t* __restrict__ prefix, uint32_t w, unsigned long long word,
+                                             uint32_t b) {
+    return prefix[w] + (uint32_t)__popcll(word & ((1ull << b) - 1ull));
+}
+
 // A.3 shadow walk (Amanatides-Woo) from q (voxel units) toward l over the
 // level-0 occupancy bits: 1 = leaves the grid unblocked, 0 = hits a voxel.
 // K2 input rule (vct_spec.h): an axis whose td is not finite -- l_a == 0, or |l_a| <= 2^-128,

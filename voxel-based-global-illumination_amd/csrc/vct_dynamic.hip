@@ -6,16 +6,18 @@
 // added can be subtracted again exactly (the adds are modulo 2^64, in the packed words too,
 // whatever carried between their halves meanwhile).  An update therefore costs what the old
 // and the new layer cost, not what the scene costs:
-//   k_dyn_setup       one lane per new triangle: k1_tri_setup's arithmetic for a Kd material
-//                     (q, candidate range, the six 16.16 values, the triangle for the G-buffer
-//                     passes behind the static ones), the error word and max|value|.  The
-//                     records are kept in the context: they are the next update's retraction.
+//   k_dyn_setup       one lane per new triangle: k1_tri_setup's arithmetic for a Kd material,
+//                     from the same pieces (vct_voxel_sat.h: q, candidate range, the six 16.16
+//                     values, the triangle for the G-buffer passes behind the static ones), the
+//                     error word and max|value|.  The records are kept in the context: they
+//                     are the next update's retraction.
 //   k_dyn_scan        the exclusive scan of the candidate counts, one block (a large layer
 //                     takes K1's three scan kernels, vct_voxel_sat.h).
 //   k_dyn_candidates  one lane per 2 (triangle, voxel) candidates, grid-stride over the flat
 //                     list (the total stays on the device: nothing is read back before the
-//                     launch): the SAT, then the hit's values times `sign` into the record in
-//                     the layout the grid has (4 or 7 atomics, none returning).  The old
+//                     launch): K1's walk (for_each_hit, vct_voxel_sat.h), then the hit's values
+//                     times `sign` into the record in the layout the grid has (4 or 7 atomics,
+//                     none returning).  The old
 //                     layer's records run with sign -1, the new layer's with +1; the +1 pass
 //                     also sets the voxel's bit in the layer's bit mask (no first-hit logic:
 //                     with both signs in flight a count of 0 proves nothing).
@@ -74,7 +76,7 @@ unsigned long long* rec_offs(const DynLayer& l) {
 }
 DynHead* rec_head(const DynLayer& l) { return (DynHead*)((char*)l.rec + kRecBytes * l.cap); }
 
-// k1_tri_setup (vct_voxelize.hip) for a Kd material: the same operations in the same order
+// k1_tri_setup (vct_voxelize.hip) for a Kd material: the same pieces, without the diffuse maps
 __global__ void __launch_bounds__(256) k_dyn_setup(const char* __restrict__ verts, uint32_t stride, uint32_t n_verts,
                                                    const uint32_t* __restrict__ idx, uint32_t n_tri,
                                                    const uint32_t* __restrict__ mat, const float4* __restrict__ kd,
@@ -84,94 +86,33 @@ __global__ void __launch_bounds__(256) k_dyn_setup(const char* __restrict__ vert
                                                    float4* __restrict__ mesh_tri, DynHead* __restrict__ head) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_tri) return;
-    const uint32_t vi[3] = {idx[3 * t], idx[3 * t + 1], idx[3 * t + 2]};
     const uint32_t m = mat ? mat[t] : 0u;
-    TriGeom g;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) g.q[i] = 0.0f;
-    g.lo[0] = g.lo[1] = g.lo[2] = 0;
-    g.ext[0] = g.ext[1] = g.ext[2] = 0;
-    g.pad = 0;
-    DynFix f;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) f.fix[i] = 0;
-    const float4 z4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (vi[0] >= n_verts || vi[1] >= n_verts || vi[2] >= n_verts || (kd && m >= n_mat)) {
+    const float z[3] = {0.0f, 0.0f, 0.0f};
+    uint32_t vi[3];
+    float p[3][3], q[3][3];
+    if ((kd && m >= n_mat) || !load_tri(verts, stride, n_verts, idx, t, g0x, g0y, g0z, inv_h, vi, p, q)) {
         atomicOr(&head->err, kK1ErrIndex);
-        geom[t] = g;
-        fixo[t] = f;
-        counts[t] = 0;
-        mesh_tri[4 * t + 0] = z4; mesh_tri[4 * t + 1] = z4; mesh_tri[4 * t + 2] = z4;
-        mesh_tri[4 * t + 3] = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
+        reject_tri(geom, counts, t);
+        store_mesh_tri(mesh_tri, t, z, z, z, make_float4(0.0f, 0.0f, 0.0f, 0.0f), -1);
         return;
     }
     const float4 alb = kd ? kd[m] : make_float4(1.0f, 1.0f, 1.0f, 1.0f);
-    float p[3][3], q[3][3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float* src = (const float*)(verts + (size_t)vi[k] * stride);
-        p[k][0] = src[0]; p[k][1] = src[1]; p[k][2] = src[2];
-        q[k][0] = (p[k][0] - g0x) * inv_h;
-        q[k][1] = (p[k][1] - g0y) * inv_h;
-        q[k][2] = (p[k][2] - g0z) * inv_h;
-    }
-    const bool kd_ok = (fabsf(alb.x) < VCT_KD_LIMIT) & (fabsf(alb.y) < VCT_KD_LIMIT) & (fabsf(alb.z) < VCT_KD_LIMIT);
-    bool finite = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-        finite &= (fabsf(q[k][0]) < __builtin_inff()) & (fabsf(q[k][1]) < __builtin_inff()) &
-                  (fabsf(q[k][2]) < __builtin_inff());
-    if (!kd_ok || !finite) {   // the K1 input rule: an error, or a skipped triangle (a zero one for the G-buffer)
+    const bool kd_ok = kd_legal(alb.x, alb.y, alb.z);
+    if (!kd_ok || !tri_finite(q)) {   // the K1 input rule: an error, or a skipped triangle (a zero one for the G-buffer)
         if (!kd_ok) atomicOr(&head->err, kK1ErrKd);
-        geom[t] = g;
-        fixo[t] = f;
-        counts[t] = 0;
-        mesh_tri[4 * t + 0] = z4; mesh_tri[4 * t + 1] = z4; mesh_tri[4 * t + 2] = z4;
-        mesh_tri[4 * t + 3] = make_float4(alb.x, alb.y, alb.z, __int_as_float(-1));
+        reject_tri(geom, counts, t);
+        store_mesh_tri(mesh_tri, t, z, z, z, alb, -1);
         return;
     }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { g.q[3 * k] = q[k][0]; g.q[3 * k + 1] = q[k][1]; g.q[3 * k + 2] = q[k][2]; }
-    float e1[3] = {p[1][0] - p[0][0], p[1][1] - p[0][1], p[1][2] - p[0][2]};
-    float e2[3] = {p[2][0] - p[0][0], p[2][1] - p[0][1], p[2][2] - p[0][2]};
-    float fn[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2],
-                   e1[0] * e2[1] - e1[1] * e2[0]};
-    float len = sqrtf(dot3(fn[0], fn[1], fn[2], fn[0], fn[1], fn[2]));
-    if (len > 0.0f) { fn[0] = fn[0] / len; fn[1] = fn[1] / len; fn[2] = fn[2] / len; }
-    else { fn[0] = 0.0f; fn[1] = 0.0f; fn[2] = 0.0f; }
-    f.fix[0] = (long long)roundf(alb.x * VCT_FIXED_ONE);
-    f.fix[1] = (long long)roundf(alb.y * VCT_FIXED_ONE);
-    f.fix[2] = (long long)roundf(alb.z * VCT_FIXED_ONE);
-    f.fix[3] = (long long)roundf(fn[0] * VCT_FIXED_ONE);
-    f.fix[4] = (long long)roundf(fn[1] * VCT_FIXED_ONE);
-    f.fix[5] = (long long)roundf(fn[2] * VCT_FIXED_ONE);
-    {
-        unsigned long long mx = 0;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const unsigned long long a = (unsigned long long)(f.fix[i] < 0 ? -f.fix[i] : f.fix[i]);
-            mx = a > mx ? a : mx;
-        }
-        const uint32_t m32 = mx >= (1ull << 31) ? (1u << 31) : (uint32_t)mx;
-        if (m32 > __hip_atomic_load(&head->maxabs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-            atomicMax(&head->maxabs, m32);
-    }
-    unsigned long long cnt = 1;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        int lo, hi;
-        cand_range(fmin3(q[0][a], q[1][a], q[2][a]), fmax3(q[0][a], q[1][a], q[2][a]), n, lo, hi);
-        g.lo[a] = lo;
-        g.ext[a] = hi >= lo ? (uint32_t)(hi - lo + 1) : 0u;
-        cnt *= g.ext[a];
-    }
+    TriGeom g;
+    DynFix f;
+    float e1[3], e2[3];
+    face_fix(p, alb, f.fix, e1, e2);
+    fix_maxabs(f.fix, &head->maxabs);
+    counts[t] = tri_range(q, n, g);
     geom[t] = g;
     fixo[t] = f;
-    counts[t] = cnt;
-    mesh_tri[4 * t + 0] = make_float4(p[0][0], p[0][1], p[0][2], 0.0f);
-    mesh_tri[4 * t + 1] = make_float4(e1[0], e1[1], e1[2], 0.0f);
-    mesh_tri[4 * t + 2] = make_float4(e2[0], e2[1], e2[2], 0.0f);
-    mesh_tri[4 * t + 3] = make_float4(alb.x, alb.y, alb.z, __int_as_float(-1));
+    store_mesh_tri(mesh_tri, t, p[0], e1, e2, alb, -1);
 }
 
 // the exclusive scan of a layer's candidate counts in one block (k_scan_carry's loop over the
@@ -202,8 +143,7 @@ __global__ void __launch_bounds__(kScanBlock) k_dyn_scan(const unsigned long lon
 
 // One lane = kDynCandPerThread consecutive candidates per sweep of the flat list.  NEG: the
 // values are subtracted (two's complement: the modular inverse of what the +1 pass added).
-// layer_bits (the +1 pass): the hit voxel's bit.  Every index is bounded: t < n_tri by the
-// search over offs[0 .. n_tri), the voxel by cand_range's clamp to [0, n - 1].
+// layer_bits (the +1 pass): the hit voxel's bit.
 template <bool PACKED, bool NEG>
 __global__ void __launch_bounds__(256) k_dyn_candidates(const TriGeom* __restrict__ geom, const DynFix* __restrict__ fixr,
                                                         const unsigned long long* __restrict__ offs, uint32_t n_tri,
@@ -214,32 +154,10 @@ __global__ void __launch_bounds__(256) k_dyn_candidates(const TriGeom* __restric
     const unsigned long long sweep = (unsigned long long)gridDim.x * blockDim.x * kDynCandPerThread;
     for (unsigned long long c0 = ((unsigned long long)blockIdx.x * blockDim.x + threadIdx.x) * kDynCandPerThread; c0 < total;
          c0 += sweep) {
-        // the last triangle whose first candidate is <= c0 (zero-count triangles share their
-        // successor's offset, so the search lands past them); a layer is a few thousand
-        // triangles: a dozen steps
-        uint32_t lo = 0, hi = n_tri;
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (offs[mid] <= c0) lo = mid; else hi = mid;
-        }
-        uint32_t t = lo;
-        unsigned long long next = t + 1 < n_tri ? offs[t + 1] : total;
-        for (int k = 0; k < kDynCandPerThread; ++k) {
-            const unsigned long long c = c0 + k;
-            if (c >= total) break;
-            while (c >= next) { ++t; next = t + 1 < n_tri ? offs[t + 1] : total; }
-            const TriGeom& g = geom[t];
-            const unsigned long long local = c - offs[t];
-            const uint32_t ex = g.ext[0], ey = g.ext[1];
-            const uint32_t x = (uint32_t)(local % ex);
-            const unsigned long long r = local / ex;
-            const uint32_t y = (uint32_t)(r % ey);
-            const uint32_t z = (uint32_t)(r / ey);
-            const int vx = g.lo[0] + (int)x, vy = g.lo[1] + (int)y, vz = g.lo[2] + (int)z;
-            float q[9];
-#pragma unroll
-            for (int i = 0; i < 9; ++i) q[i] = g.q[i];
-            if (!tri_box_overlap(q, (float)vx + 0.5f, (float)vy + 0.5f, (float)vz + 0.5f)) continue;
+        // the whole list is searched: a layer is a few thousand triangles, a dozen steps
+        const uint32_t t0 = find_tri(offs, 0, n_tri, c0);
+        for_each_hit<kDynCandPerThread>(geom, offs, n_tri, total, c0, t0,
+                                        [&](uint32_t t, int vx, int vy, int vz, const float*) __attribute__((always_inline)) {
             const size_t v = (size_t)vx + (size_t)n * ((size_t)vy + (size_t)n * (size_t)vz);
             unsigned long long* a = (unsigned long long*)(accum + 8 * v);
             const DynFix& f = fixr[t];
@@ -258,7 +176,7 @@ __global__ void __launch_bounds__(256) k_dyn_candidates(const TriGeom* __restric
                 atomicAdd(a + 6, NEG ? ~0ull : 1ull);
             }
             if (layer_bits) atomicOr(layer_bits + (v >> 6), 1ull << (v & 63));
-        }
+        });
     }
 }
 
@@ -324,36 +242,15 @@ __global__ void __launch_bounds__(256) k_dyn_unpack(const uint32_t* __restrict__
     }
 }
 
-vct_status dfail(vct_ctx* c, vct_status s, const std::string& msg) {
-    c->err = msg;
-    return s;
-}
-
-vct_status dhip(vct_ctx* c, hipError_t e, const char* where) {
-    return dfail(c, e == hipErrorOutOfMemory ? VCT_ENOMEM : VCT_EDEVICE,
-                 std::string(where) + ": " + hipGetErrorName(e) + " (" + hipGetErrorString(e) + ")");
-}
-
-#define DYN_HIP(call, where)                                 \
-    do {                                                     \
-        hipError_t e_ = (call);                              \
-        if (e_ != hipSuccess) return dhip(c, e_, where);     \
-    } while (0)
-
-struct DevTmp {   // a staging buffer of the host form, freed on every exit
-    void* p = nullptr;
-    ~DevTmp() { if (p) (void)hipFree(p); }
-};
-
 // `bytes` of *p with the first `keep` bytes preserved (the static scene's triangles)
 vct_status grow_keeping(vct_ctx* c, float4*& p, size_t& cap, size_t bytes, size_t keep) {
     if (cap >= bytes) return VCT_OK;
     float4* np = nullptr;
-    DYN_HIP(hipMalloc((void**)&np, bytes), "hipMalloc mesh");
-    hipError_t e = hipSuccess;
+    hipError_t e = hipMalloc((void**)&np, bytes);
+    if (e != hipSuccess) return lhip(c, e, "hipMalloc mesh");
     if (p && keep) e = hipMemcpyAsync(np, p, keep, hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // nothing reads the old array any more
-    if (e != hipSuccess) { (void)hipFree(np); return dhip(c, e, "mesh copy"); }
+    if (e != hipSuccess) { (void)hipFree(np); return lhip(c, e, "mesh copy"); }
     if (p) (void)hipFree(p);
     p = np;
     cap = bytes;
@@ -401,24 +298,27 @@ vct_status dynamic_update(vct_ctx* c, const void* d_verts, uint32_t stride, uint
     const size_t nv = (size_t)g.n * g.n * g.n, nwords = nv / 64;
     const bool had = dynamic_live(c);
     const uint32_t n_static = had ? d.n_static : m.n_tri;
-    if ((uint64_t)n_static + n_tri > 0xffffffffull) return dfail(c, VCT_EINVAL, "voxelize_dynamic: too many triangles");
+    if ((uint64_t)n_static + n_tri > 0xffffffffull) return lfail(c, VCT_EINVAL, "voxelize_dynamic: too many triangles");
     DynLayer& old = d.layer[d.cur];
     DynLayer& nw = d.layer[1 - d.cur];
+    hipError_t e;
 
     // memory: the two bit masks, the new layer's records, the mesh behind the static triangles
-    if (!d.h_head) DYN_HIP(hipHostMalloc(&d.h_head, sizeof(DynHead), hipHostMallocDefault), "hipHostMalloc");
+    if (!d.h_head && (e = hipHostMalloc(&d.h_head, sizeof(DynHead), hipHostMallocDefault)) != hipSuccess)
+        return lhip(c, e, "hipHostMalloc");
     for (DynLayer* l : {&old, &nw})
         if (!l->bits) {
-            DYN_HIP(hipMalloc((void**)&l->bits, nwords * 8), "hipMalloc layer bits");
-            DYN_HIP(hipMemsetAsync(l->bits, 0, nwords * 8, s), "memset");
+            if ((e = hipMalloc((void**)&l->bits, nwords * 8)) != hipSuccess) return lhip(c, e, "hipMalloc layer bits");
+            if ((e = hipMemsetAsync(l->bits, 0, nwords * 8, s)) != hipSuccess) return lhip(c, e, "memset");
         }
     if (!nw.rec || nw.cap < n_tri) {
-        DYN_HIP(hipStreamSynchronize(s), "sync");
+        if ((e = hipStreamSynchronize(s)) != hipSuccess) return lhip(c, e, "sync");
         if (nw.rec) (void)hipFree(nw.rec);
         nw.rec = nullptr;
         nw.cap = 0;
         const size_t cap = std::max<size_t>(n_tri, 64);
-        DYN_HIP(hipMalloc(&nw.rec, kRecBytes * cap + sizeof(DynHead)), "hipMalloc layer records");
+        if ((e = hipMalloc(&nw.rec, kRecBytes * cap + sizeof(DynHead))) != hipSuccess)
+            return lhip(c, e, "hipMalloc layer records");
         nw.cap = cap;
     }
     const size_t all_tri = std::max<size_t>((size_t)n_static + n_tri, 1);
@@ -427,16 +327,17 @@ vct_status dynamic_update(vct_ctx* c, const void* d_verts, uint32_t stride, uint
     if (m.textured) {   // the layer's entries exist (its triangles have no diffuse map: never read)
         st = grow_keeping(c, m.uv, m.uv_cap, all_tri * 2 * sizeof(float4), (size_t)n_static * 2 * sizeof(float4));
         if (st != VCT_OK) return st;
-        if (n_tri)
-            DYN_HIP(hipMemsetAsync(m.uv + 2 * (size_t)n_static, 0, (size_t)n_tri * 2 * sizeof(float4), s), "memset uv");
+        if (n_tri && (e = hipMemsetAsync(m.uv + 2 * (size_t)n_static, 0, (size_t)n_tri * 2 * sizeof(float4), s)) != hipSuccess)
+            return lhip(c, e, "memset uv");
     }
     const uint32_t n_tiles = (n_tri + kScanTile - 1) / kScanTile;
     void* tp = nullptr;
-    DYN_HIP(scratch_get(c, kSlotTmp, 8 * (size_t)n_tri + 8 * (size_t)(n_tiles + 1) + 64, &tp), "scratch");
+    if ((e = scratch_get(c, kSlotTmp, 8 * (size_t)n_tri + 8 * (size_t)(n_tiles + 1) + 64, &tp)) != hipSuccess)
+        return lhip(c, e, "scratch");
     unsigned long long* cnt = (unsigned long long*)tp;
     unsigned long long* tiles = cnt + n_tri;
     void* lp = nullptr;
-    DYN_HIP(scratch_get(c, kSlotList, 256 + nv * 4, &lp), "scratch");
+    if ((e = scratch_get(c, kSlotList, 256 + nv * 4, &lp)) != hipSuccess) return lhip(c, e, "scratch");
     uint32_t* list = (uint32_t*)((char*)lp + 256);
 
     // what voxelize_dev invalidates; only the success path sets `voxelized` again
@@ -449,11 +350,11 @@ vct_status dynamic_update(vct_ctx* c, const void* d_verts, uint32_t stride, uint
     if (!had) {   // no layer in place: whatever the record sets hold belongs to an earlier grid
         old.n_tri = 0;
         old.total = 0;
-        DYN_HIP(hipMemsetAsync(old.bits, 0, nwords * 8, s), "memset");
+        if ((e = hipMemsetAsync(old.bits, 0, nwords * 8, s)) != hipSuccess) return lhip(c, e, "memset");
     }
     DynHead* head = rec_head(nw);
-    DYN_HIP(hipMemsetAsync(nw.bits, 0, nwords * 8, s), "memset");
-    DYN_HIP(hipMemsetAsync(head, 0, sizeof(DynHead), s), "memset");
+    if ((e = hipMemsetAsync(nw.bits, 0, nwords * 8, s)) != hipSuccess) return lhip(c, e, "memset");
+    if ((e = hipMemsetAsync(head, 0, sizeof(DynHead), s)) != hipSuccess) return lhip(c, e, "memset");
     const bool packed = g.accum_packed;
     if (old.n_tri && old.total) launch_candidates<true>(c, old, old.n_tri, blocks_for(old.total), packed, nullptr);
     if (n_tri) {
@@ -463,9 +364,7 @@ vct_status dynamic_update(vct_ctx* c, const void* d_verts, uint32_t stride, uint
         if (n_tri <= kSmallScan) {
             hipLaunchKernelGGL(k_dyn_scan, dim3(1), dim3(kScanBlock), 0, s, cnt, rec_offs(nw), n_tri, &head->total);
         } else {
-            hipLaunchKernelGGL(k_scan_tiles, dim3(n_tiles), dim3(kScanBlock), 0, s, cnt, rec_offs(nw), tiles, n_tri);
-            hipLaunchKernelGGL(k_scan_carry, dim3(1), dim3(kScanBlock), 0, s, tiles, n_tiles, &head->total);
-            hipLaunchKernelGGL(k_scan_add, dim3(n_tiles), dim3(kScanBlock), 0, s, rec_offs(nw), tiles, n_tri);
+            launch_count_scan(s, cnt, rec_offs(nw), tiles, n_tri, &head->total);
         }
         launch_candidates<false>(c, nw, n_tri, kAddBlocks, packed, nw.bits);
     }
@@ -473,16 +372,16 @@ vct_status dynamic_update(vct_ctx* c, const void* d_verts, uint32_t stride, uint
     hipLaunchKernelGGL(k_dyn_list, dim3(wb), dim3(256), 0, s, old.bits, nw.bits, nwords, list, head, g.occ_count);
     launch_fixup(c, list, nw, packed);
     hipLaunchKernelGGL(k_dyn_occ_list, dim3(wb), dim3(256), 0, s, g.occ_bits, nwords, g.occ_list, g.occ_count);
-    DYN_HIP(hipGetLastError(), "voxelize_dynamic");
-    DYN_HIP(launch_k3_live(c), "K3 live blocks");
+    if ((e = hipGetLastError()) != hipSuccess) return lhip(c, e, "voxelize_dynamic");
+    if ((e = launch_k3_live(c)) != hipSuccess) return lhip(c, e, "K3 live blocks");
     // (into pinned memory: a pageable destination makes the runtime stage the 32 bytes)
-    DYN_HIP(hipMemcpyAsync(d.h_head, head, sizeof(DynHead), hipMemcpyDeviceToHost, s), "read back");
-    DYN_HIP(hipStreamSynchronize(s), "voxelize_dynamic sync");
+    if ((e = hipMemcpyAsync(d.h_head, head, sizeof(DynHead), hipMemcpyDeviceToHost, s)) != hipSuccess) return lhip(c, e, "read back");
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return lhip(c, e, "voxelize_dynamic sync");
     const DynHead h = *(const DynHead*)d.h_head;
     // a grid from out-of-range indices or an illegal Kd is partial: refused until a vct_voxelize*
-    if (h.err & kK1ErrKd) return dfail(c, VCT_EINVAL, kKdMessage);
-    if (h.err & kK1ErrIndex) return dfail(c, VCT_EINVAL, "voxelize_dynamic: vertex or material index out of range");
-    if ((size_t)h.n_touched > nv || (size_t)h.n_voxels > nv) return dfail(c, VCT_EDEVICE, "voxelize_dynamic: count out of range");
+    if (h.err & kK1ErrKd) return lfail(c, VCT_EINVAL, kKdMessage);
+    if (h.err & kK1ErrIndex) return lfail(c, VCT_EINVAL, "voxelize_dynamic: vertex or material index out of range");
+    if ((size_t)h.n_touched > nv || (size_t)h.n_voxels > nv) return lfail(c, VCT_EDEVICE, "voxelize_dynamic: count out of range");
     if (packed && (h.redo & kK1ErrRedo)) {
         // the packed records cannot hold the union: take the layer out again (exact, whatever
         // overflowed meanwhile), unpack what is left, and add the layer in the seven-atomic form
@@ -492,7 +391,7 @@ vct_status dynamic_update(vct_ctx* c, const void* d_verts, uint32_t stride, uint
         g.accum_packed = false;
         if (n_tri && h.total) launch_candidates<false>(c, nw, n_tri, blocks_for(h.total), false, nullptr);
         launch_fixup(c, list, nw, false);
-        DYN_HIP(hipGetLastError(), "voxelize_dynamic (unpacked)");
+        if ((e = hipGetLastError()) != hipSuccess) return lhip(c, e, "voxelize_dynamic (unpacked)");
     }
     nw.n_tri = n_tri;
     nw.total = h.total;
@@ -508,14 +407,14 @@ vct_status dynamic_update(vct_ctx* c, const void* d_verts, uint32_t stride, uint
 
 vct_status dynamic_args(vct_ctx* c, const void* verts, uint32_t stride, uint32_t n_idx, const uint32_t* idx,
                         const float* kd4, uint32_t n_mat) {
-    if (!c->grid.voxelized) return dfail(c, VCT_ESTATE, "voxelize_dynamic without a static grid (voxelize first)");
-    if (n_idx % 3 != 0) return dfail(c, VCT_EINVAL, "voxelize_dynamic: n_idx must be a multiple of 3");
-    if (n_idx > 0 && (!verts || !idx)) return dfail(c, VCT_EINVAL, "voxelize_dynamic: null vertex or index array");
+    if (!c->grid.voxelized) return lfail(c, VCT_ESTATE, "voxelize_dynamic without a static grid (voxelize first)");
+    if (n_idx % 3 != 0) return lfail(c, VCT_EINVAL, "voxelize_dynamic: n_idx must be a multiple of 3");
+    if (n_idx > 0 && (!verts || !idx)) return lfail(c, VCT_EINVAL, "voxelize_dynamic: null vertex or index array");
     if (stride < 12 || stride % 4 != 0)
-        return dfail(c, VCT_EINVAL, "voxelize_dynamic: vertex_stride < 12 or not a multiple of 4");
-    if (kd4 && n_mat == 0) return dfail(c, VCT_EINVAL, "voxelize_dynamic: material_kd4 with n_materials == 0");
+        return lfail(c, VCT_EINVAL, "voxelize_dynamic: vertex_stride < 12 or not a multiple of 4");
+    if (kd4 && n_mat == 0) return lfail(c, VCT_EINVAL, "voxelize_dynamic: material_kd4 with n_materials == 0");
     hipError_t e = hipSetDevice(c->device);
-    if (e != hipSuccess) return dhip(c, e, "hipSetDevice");
+    if (e != hipSuccess) return lhip(c, e, "hipSetDevice");
     return VCT_OK;
 }
 
@@ -541,7 +440,7 @@ extern "C" vct_status vct_voxelize_dynamic_device(vct_ctx* c, const void* verts,
     vct_status st = dynamic_args(c, verts, stride, n_idx, idx, kd4, n_mat);
     if (st != VCT_OK) return st;
     if (((uintptr_t)kd4 & 15) || ((uintptr_t)verts & 3) || ((uintptr_t)idx & 3) || ((uintptr_t)tri_mat & 3))
-        return dfail(c, VCT_EINVAL, "voxelize_dynamic: material_kd4 must be 16-byte, verts, idx and tri_material "
+        return lfail(c, VCT_EINVAL, "voxelize_dynamic: material_kd4 must be 16-byte, verts, idx and tri_material "
                                     "4-byte aligned");
     return dynamic_update(c, verts, stride, n_verts, idx, n_idx / 3, tri_mat, (const float4*)kd4, n_mat);
 }
@@ -556,35 +455,21 @@ extern "C" vct_status vct_voxelize_dynamic(vct_ctx* c, const void* verts, uint32
     // the Kd rule on the host, before any launch: the Kd of every material a triangle uses (an
     // out-of-range material index is the setup kernel's to report).  Unlike vct_voxelize, which
     // has nothing to fall back to, the grid and the layer in place stay as they are
-    if (kd4)
-        for (uint32_t t = 0; t < n_tri; ++t) {
-            const uint32_t m = tri_mat ? tri_mat[t] : 0u;
-            if (m >= n_mat) continue;
-            const float* k = kd4 + 4 * (size_t)m;
-            if (!(fabsf(k[0]) < VCT_KD_LIMIT && fabsf(k[1]) < VCT_KD_LIMIT && fabsf(k[2]) < VCT_KD_LIMIT))
-                return dfail(c, VCT_EINVAL, kKdMessage);
-        }
-    DevTmp dv, di, dm, dk;
-    const size_t vbytes = (size_t)stride * n_verts;
-    if (vbytes) DYN_HIP(hipMalloc(&dv.p, vbytes), "hipMalloc verts");
-    if (n_idx) DYN_HIP(hipMalloc(&di.p, (size_t)n_idx * 4), "hipMalloc idx");
-    if (tri_mat && n_tri) DYN_HIP(hipMalloc(&dm.p, (size_t)n_tri * 4), "hipMalloc mat");
-    if (kd4) DYN_HIP(hipMalloc(&dk.p, (size_t)n_mat * 16), "hipMalloc kd");
-    if (vbytes) DYN_HIP(hipMemcpyAsync(dv.p, verts, vbytes, hipMemcpyHostToDevice, c->stream), "upload verts");
-    if (n_idx) DYN_HIP(hipMemcpyAsync(di.p, idx, (size_t)n_idx * 4, hipMemcpyHostToDevice, c->stream), "upload idx");
-    if (dm.p) DYN_HIP(hipMemcpyAsync(dm.p, tri_mat, (size_t)n_tri * 4, hipMemcpyHostToDevice, c->stream), "upload mat");
-    if (dk.p) DYN_HIP(hipMemcpyAsync(dk.p, kd4, (size_t)n_mat * 16, hipMemcpyHostToDevice, c->stream), "upload kd");
+    if (!used_kd_legal(tri_mat, n_tri, kd4, n_mat)) return lfail(c, VCT_EINVAL, kKdMessage);
+    MeshStage ms;
+    if ((st = stage_mesh(c, ms, verts, (size_t)stride * n_verts, idx, n_idx, tri_mat, kd4, "kd", nullptr, n_mat)) != VCT_OK)
+        return st;
     // (dynamic_update waits for the stream after the last kernel that reads the staging buffers)
-    return dynamic_update(c, dv.p, stride, n_verts, (const uint32_t*)di.p, n_tri, (const uint32_t*)dm.p,
-                          (const float4*)dk.p, n_mat);
+    return dynamic_update(c, ms.verts.p, stride, n_verts, (const uint32_t*)ms.idx.p, n_tri, (const uint32_t*)ms.mat.p,
+                          (const float4*)ms.mats.p, n_mat);
 }
 
 // test hook (not part of the headers): 1 / 0 = the grid's records are packed / one sum per word
 extern "C" int vct_debug_accum_packed(const vct_ctx* c) { return c && c->grid.accum_packed ? 1 : 0; }
 
 extern "C" vct_status vct_dynamic_voxels(vct_ctx* c, uint32_t* n_touched) {
-    if (!c || !n_touched) return c ? dfail(c, VCT_EINVAL, "dynamic_voxels: null output") : VCT_EINVAL;
-    if (!c->grid.voxelized) return dfail(c, VCT_ESTATE, "dynamic_voxels before voxelize");
+    if (!c || !n_touched) return c ? lfail(c, VCT_EINVAL, "dynamic_voxels: null output") : VCT_EINVAL;
+    if (!c->grid.voxelized) return lfail(c, VCT_ESTATE, "dynamic_voxels before voxelize");
     *n_touched = dynamic_live(c) ? c->dyn.n_voxels : 0u;
     return VCT_OK;
 }

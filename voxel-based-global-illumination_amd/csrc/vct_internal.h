@@ -374,6 +374,66 @@ inline const char* check_color(const float* color) {
     return nullptr;
 }
 
+// a failed call: its text for vct_last_error and its status
+inline vct_status lfail(vct_ctx* c, vct_status s, const std::string& msg) {
+    c->err = msg;
+    return s;
+}
+
+inline vct_status lhip(vct_ctx* c, hipError_t e, const char* where) {
+    return lfail(c, e == hipErrorOutOfMemory ? VCT_ENOMEM : VCT_EDEVICE,
+                 std::string(where) + ": " + hipGetErrorName(e) + " (" + hipGetErrorString(e) + ")");
+}
+
+// K1 input rule, Kd (vct_spec.h): finite and |Kd| < VCT_KD_LIMIT (a NaN fails the compare)
+// (`&`, not `&&`: in a kernel, short-circuit evaluation would make each load wait for the one before it)
+__host__ __device__ __forceinline__ bool kd_legal(float r, float g, float b) {
+    return ((int)(fabsf(r) < VCT_KD_LIMIT) & (int)(fabsf(g) < VCT_KD_LIMIT) & (int)(fabsf(b) < VCT_KD_LIMIT)) != 0;
+}
+
+// The Kd rule on the host, before any launch: the Kd of every material a triangle uses (an
+// out-of-range material index is the setup kernel's to report); false: one is illegal
+inline bool used_kd_legal(const uint32_t* tri_mat, uint32_t n_tri, const float* kd4, uint32_t n_mat) {
+    for (uint32_t t = 0; kd4 && t < n_tri; ++t) {
+        const uint32_t m = tri_mat ? tri_mat[t] : 0u;
+        if (m >= n_mat) continue;
+        const float* k = kd4 + 4 * (size_t)m;
+        if (!kd_legal(k[0], k[1], k[2])) return false;
+    }
+    return true;
+}
+
+// The device copies of a host-form voxelization's arrays, freed on every exit: whatever reads
+// them must have run by then (the caller waits for the ctx stream)
+struct DevTmp {
+    void* p = nullptr;
+    ~DevTmp() { if (p) (void)hipFree(p); }
+};
+struct MeshStage {
+    DevTmp verts, idx, mat, mats, map;
+};
+
+// Allocates them and queues the uploads on the ctx stream.  tri_mat, mats4 (n_mat records of 16
+// bytes: Kd or Ke, `mats_name` in the error text) and map (n_mat words) may be NULL
+inline vct_status stage_mesh(vct_ctx* c, MeshStage& s, const void* verts, size_t vbytes, const uint32_t* idx,
+                             uint32_t n_idx, const uint32_t* tri_mat, const float* mats4, const char* mats_name,
+                             const int32_t* map, uint32_t n_mat) {
+    const struct { DevTmp& d; const void* src; size_t bytes; const char* name; } a[5] = {
+        {s.verts, verts, vbytes, "verts"},
+        {s.idx, idx, (size_t)n_idx * 4, "idx"},
+        {s.mat, tri_mat, tri_mat ? (size_t)(n_idx / 3) * 4 : 0, "mat"},
+        {s.mats, mats4, mats4 ? (size_t)n_mat * 16 : 0, mats_name},
+        {s.map, map, map ? (size_t)n_mat * 4 : 0, "map"}};
+    hipError_t e;
+    for (const auto& x : a)
+        if (x.bytes && (e = hipMalloc(&x.d.p, x.bytes)) != hipSuccess)
+            return lhip(c, e, (std::string("hipMalloc ") + x.name).c_str());
+    for (const auto& x : a)
+        if (x.bytes && (e = hipMemcpyAsync(x.d.p, x.src, x.bytes, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
+            return lhip(c, e, (std::string("upload ") + x.name).c_str());
+    return VCT_OK;
+}
+
 // K1
 // d_map (device, n_mat entries, may be NULL): diffuse map of each material in c->tex
 // (-1 none); uv_offset: byte offset of the TexCoords in a vertex record (read when d_map).
@@ -449,6 +509,21 @@ hipError_t launch_untile(vct_ctx* c, const float4* gathered, uint32_t planes, ui
 hipError_t launch_composite(vct_ctx* c, const float4* pos, const float4* nrm, const float4* alb,
                             const float4* diff, const float4* spec, uint32_t w, uint32_t h, const float l[3],
                             const float color[3], float4* lin, uint32_t* rgba8);
+// Composite + present for a light list (vct_lights.hip), behind vct_composite_lights_device,
+// _shadowed_device and _emissive_device (`what`: the entry point, for the error text): the
+// argument checks the three share, in their order; then the caller's own rule; then the light
+// list's, and one kernel.  What differs between the entry points:
+struct CompositeForm {
+    const float* vis = nullptr;        // [n_lights][h][w]
+    bool read_vis = false;             // V is read from vis, else walked
+    float scale = 0.0f;
+    bool emit = false;                 // scale * E of the pixel's voxel is added
+    const char* own_error = nullptr;   // the caller's own rule is broken: "<what>: <own_error>" is the error
+};
+vct_status composite_light_list(vct_ctx* c, const char* what, const float* pos4, const float* nrm4, const float* alb4,
+                                const float* diffuse4, const float* spec4, uint32_t w, uint32_t h,
+                                const vct_light* lights, uint32_t n_lights, const CompositeForm& form,
+                                float* out_linear4, uint32_t* out_rgba8);
 // G-buffer
 hipError_t launch_gbuffer_binned(vct_ctx* c, const vct_camera* cam, uint32_t w, uint32_t h, float rough,
                                  float4* pos, float4* nrm, float4* alb);

@@ -140,16 +140,6 @@ float grid_h2(const Grid& g) {
     return hh * hh;
 }
 
-vct_status lfail(vct_ctx* c, vct_status s, const std::string& msg) {
-    c->err = msg;
-    return s;
-}
-
-vct_status lhip(vct_ctx* c, hipError_t e, const char* where) {
-    return lfail(c, e == hipErrorOutOfMemory ? VCT_ENOMEM : VCT_EDEVICE,
-                 std::string(where) + ": " + hipGetErrorName(e) + " (" + hipGetErrorString(e) + ")");
-}
-
 vct_status prepare_list(vct_ctx* c, const char* what, const vct_light* lights, uint32_t n, DLight* out) {
     if (n > VCT_MAX_LIGHTS) return lfail(c, VCT_EINVAL, std::string(what) + ": more than VCT_MAX_LIGHTS lights");
     if (n && !lights) return lfail(c, VCT_EINVAL, std::string(what) + ": NULL lights");

@@ -17,6 +17,11 @@
 //              operations, so the same bits), times the mask bit, added in list order.
 // The first batch writes level 0, later ones add to it.  The plain form (one light per
 // pass: pairs -> walk -> sum with a batch of one) is the A/B baseline, vct_debug_lights.
+//
+// The composite of a light list is one kernel, kl_composite<VIS, EM>, behind three entry
+// points: vct_composite_lights_device here (V walked), vct_composite_shadowed_device
+// (vct_shadow.hip: V read from a vis plane) and vct_composite_emissive_device (vct_emission.hip:
+// either, plus the emission term).  composite_light_list has the checks they share.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <atomic>
@@ -274,20 +279,29 @@ __global__ void __launch_bounds__(256) kl_sum(const uint32_t* __restrict__ occ, 
 }
 
 // ---- composite + present for a light list (k_composite, vct_frame.hip, with the direct
-// term of the spec): one lane per pixel, the lights in list order, the plain walk ----------
-struct CompLK {
+// term of the spec): one lane per pixel, the lights in list order ---------------------------
+struct CompK {
     const float4 *pos, *nrm, *alb, *diff, *spec;
-    const unsigned long long* bits;
+    const float* vis;                      // VIS: [n_lights][h][w]
+    const unsigned long long* bits;        // !VIS: K1's occupancy, for the walk
+    const unsigned long long* em_bits;     // EM: the emission grid (Emission, vct_internal.h)
+    const uint32_t* em_prefix;
+    const float4* em_E;
     int n, w, h;
-    float g0x, g0y, g0z, inv_h, h2;
+    float g0x, g0y, g0z, inv_h, h2, scale;
     uint32_t n_lights;
     float4* lin;
     uint32_t* rgba8;
 };
 
-__global__ void __launch_bounds__(256) kl_composite(const CompLK k, const LightSet set) {
+// VIS: V read from the vis plane (vct_composite_shadowed_device), else the plain walk; EM: the
+// grid may hold an emissive voxel and scale != 0 (vct_composite_emissive_device; without it,
+// the arithmetic of the other two, unchanged)
+template <bool VIS, bool EM>
+__global__ void __launch_bounds__(256) kl_composite(const CompK k, const LightSet set) {
+    const uint32_t npx = (uint32_t)k.w * (uint32_t)k.h;
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= (uint32_t)k.w * (uint32_t)k.h) return;
+    if (i >= npx) return;
     const float4 P = k.pos[i];
     if (P.w == 0.0f) {   // background: the reference's clear colour
         if (k.lin) k.lin[i] = make_float4(VCT_CLEAR_R, VCT_CLEAR_G, VCT_CLEAR_B, 0.0f);
@@ -297,19 +311,39 @@ __global__ void __launch_bounds__(256) kl_composite(const CompLK k, const LightS
         return;
     }
     const float4 N = k.nrm[i], A = k.alb[i], D = k.diff[i], S = k.spec[i];
-    const float qx = (P.x - k.g0x) * k.inv_h + N.x, qy = (P.y - k.g0y) * k.inv_h + N.y,
-                qz = (P.z - k.g0z) * k.inv_h + N.z;
+    const float px = (P.x - k.g0x) * k.inv_h, py = (P.y - k.g0y) * k.inv_h, pz = (P.z - k.g0z) * k.inv_h;
+    const float qx = px + N.x, qy = py + N.y, qz = pz + N.z;
     float dr = 0.0f, dg = 0.0f, db = 0.0f;
     for (uint32_t j = 0; j < k.n_lights; ++j) {
         const DLight& L = set.l[j];
         float lx, ly, lz, f, ndl, t_lim;
         if (!light_terms(L, k.h2, qx, qy, qz, N.x, N.y, N.z, lx, ly, lz, f, ndl, t_lim)) continue;
-        const float vis = dda_lim(k.bits, k.n, qx, qy, qz, lx, ly, lz, t_lim);
+        float vis;
+        if constexpr (VIS) vis = k.vis[(size_t)j * npx + i];
+        else vis = dda_lim(k.bits, k.n, qx, qy, qz, lx, ly, lz, t_lim);
         dr = dr + (((A.x * L.cr) * ndl) * f) * vis;
         dg = dg + (((A.y * L.cg) * ndl) * f) * vis;
         db = db + (((A.z * L.cb) * ndl) * f) * vis;
     }
-    const float fr = (dr + A.x * D.x) + S.x, fg = (dg + A.y * D.y) + S.y, fb = (db + A.z * D.z) + S.z;
+    float fr = (dr + A.x * D.x) + S.x, fg = (dg + A.y * D.y) + S.y, fb = (db + A.z * D.z) + S.z;
+    if constexpr (EM) {
+        // Em = E of the voxel holding P itself (no normal offset); +0 outside the grid (a NaN
+        // fails the compares) and at a voxel that does not emit
+        float er = 0.0f, eg = 0.0f, eb = 0.0f;
+        const float fn = (float)k.n;
+        if (px >= 0.0f && px < fn && py >= 0.0f && py < fn && pz >= 0.0f && pz < fn) {
+            const uint32_t v = (uint32_t)(int)floorf(px) +
+                               (uint32_t)k.n * ((uint32_t)(int)floorf(py) + (uint32_t)k.n * (uint32_t)(int)floorf(pz));
+            const unsigned long long word = k.em_bits[v >> 6];
+            if ((word >> (v & 63u)) & 1ull) {
+                const float4 e = k.em_E[bit_rank(k.em_prefix, v >> 6, word, v & 63u)];
+                er = e.x; eg = e.y; eb = e.z;
+            }
+        }
+        fr = fr + k.scale * er;
+        fg = fg + k.scale * eg;
+        fb = fb + k.scale * eb;
+    }
     if (k.lin) k.lin[i] = make_float4(fr, fg, fb, 1.0f);
     if (k.rgba8) k.rgba8[i] = to8(fr) | (to8(fg) << 8) | (to8(fb) << 16) | (255u << 24);
 }
@@ -403,6 +437,52 @@ hipError_t launch_lights(vct_ctx* c, const DLight* lights, uint32_t n_lights) {
 }
 
 }  // namespace
+
+vct_status composite_light_list(vct_ctx* c, const char* what, const float* pos4, const float* nrm4, const float* alb4,
+                                const float* diffuse4, const float* spec4, uint32_t w, uint32_t h,
+                                const vct_light* lights, uint32_t n_lights, const CompositeForm& form,
+                                float* out_linear4, uint32_t* out_rgba8) {
+    if (!c || !pos4 || !nrm4 || !alb4 || !diffuse4 || !spec4 || w == 0 || h == 0) return VCT_EINVAL;
+    if (!out_linear4 && !out_rgba8) return lfail(c, VCT_EINVAL, "composite: no output");
+    if ((uint64_t)w * h > 0x7fffffffull) return lfail(c, VCT_EINVAL, "composite: frame too large");
+    if (!c->grid.voxelized) return lfail(c, VCT_ESTATE, "composite before voxelize");
+    for (const void* p : {(const void*)pos4, (const void*)nrm4, (const void*)alb4, (const void*)diffuse4,
+                          (const void*)spec4, (const void*)out_linear4})
+        if (((uintptr_t)p & 15u) != 0) return lfail(c, VCT_EINVAL, "composite: float4 buffers must be 16-byte aligned");
+    if (((uintptr_t)out_rgba8 & 3u) != 0) return lfail(c, VCT_EINVAL, "composite: rgba8 buffer must be 4-byte aligned");
+    if (form.own_error) return lfail(c, VCT_EINVAL, std::string(what) + ": " + form.own_error);
+    LightSet set;
+    std::memset(&set, 0, sizeof set);
+    vct_status st = prepare_list(c, what, lights, n_lights, set.l);
+    if (st != VCT_OK) return st;
+    hipError_t e = hipSetDevice(c->device);
+    if (e != hipSuccess) return lhip(c, e, "hipSetDevice");
+    const Grid& g = c->grid;
+    const Emission& em = c->em;
+    CompK k;
+    std::memset(&k, 0, sizeof k);
+    k.pos = (const float4*)pos4; k.nrm = (const float4*)nrm4; k.alb = (const float4*)alb4;
+    k.diff = (const float4*)diffuse4; k.spec = (const float4*)spec4;
+    k.vis = form.vis;
+    k.bits = g.occ_bits;
+    k.em_bits = em.bits; k.em_prefix = em.prefix; k.em_E = em.E;
+    k.n = (int)g.n; k.w = (int)w; k.h = (int)h;
+    k.g0x = g.g0[0]; k.g0y = g.g0[1]; k.g0z = g.g0[2]; k.inv_h = g.inv_h; k.h2 = grid_h2(g);
+    k.scale = form.scale;
+    k.n_lights = n_lights;
+    k.lin = (float4*)out_linear4; k.rgba8 = out_rgba8;
+    const dim3 grid((w * h + 255) / 256), block(256);
+    if (form.read_vis) {
+        if (form.emit) hipLaunchKernelGGL((kl_composite<true, true>), grid, block, 0, c->stream, k, set);
+        else hipLaunchKernelGGL((kl_composite<true, false>), grid, block, 0, c->stream, k, set);
+    } else {
+        if (form.emit) hipLaunchKernelGGL((kl_composite<false, true>), grid, block, 0, c->stream, k, set);
+        else hipLaunchKernelGGL((kl_composite<false, false>), grid, block, 0, c->stream, k, set);
+    }
+    if ((e = hipGetLastError()) != hipSuccess) return lhip(c, e, what);
+    return VCT_OK;
+}
+
 }  // namespace vct
 
 using namespace vct;
@@ -431,32 +511,8 @@ extern "C" vct_status vct_composite_lights_device(vct_ctx* c, const float* pos4,
                                                   const float* diffuse4, const float* spec4, uint32_t w, uint32_t h,
                                                   const vct_light* lights, uint32_t n_lights, float* out_linear4,
                                                   uint32_t* out_rgba8) {
-    if (!c || !pos4 || !nrm4 || !alb4 || !diffuse4 || !spec4 || w == 0 || h == 0) return VCT_EINVAL;
-    if (!out_linear4 && !out_rgba8) return lfail(c, VCT_EINVAL, "composite: no output");
-    if ((uint64_t)w * h > 0x7fffffffull) return lfail(c, VCT_EINVAL, "composite: frame too large");
-    if (!c->grid.voxelized) return lfail(c, VCT_ESTATE, "composite before voxelize");
-    for (const void* p : {(const void*)pos4, (const void*)nrm4, (const void*)alb4, (const void*)diffuse4,
-                          (const void*)spec4, (const void*)out_linear4})
-        if (((uintptr_t)p & 15u) != 0) return lfail(c, VCT_EINVAL, "composite: float4 buffers must be 16-byte aligned");
-    if (((uintptr_t)out_rgba8 & 3u) != 0) return lfail(c, VCT_EINVAL, "composite: rgba8 buffer must be 4-byte aligned");
-    LightSet set;
-    std::memset(&set, 0, sizeof set);
-    vct_status st = prepare_list(c, "composite_lights", lights, n_lights, set.l);
-    if (st != VCT_OK) return st;
-    hipError_t e = hipSetDevice(c->device);
-    if (e != hipSuccess) return lhip(c, e, "hipSetDevice");
-    const Grid& g = c->grid;
-    CompLK k;
-    k.pos = (const float4*)pos4; k.nrm = (const float4*)nrm4; k.alb = (const float4*)alb4;
-    k.diff = (const float4*)diffuse4; k.spec = (const float4*)spec4;
-    k.bits = g.occ_bits;
-    k.n = (int)g.n; k.w = (int)w; k.h = (int)h;
-    k.g0x = g.g0[0]; k.g0y = g.g0[1]; k.g0z = g.g0[2]; k.inv_h = g.inv_h; k.h2 = grid_h2(g);
-    k.n_lights = n_lights;
-    k.lin = (float4*)out_linear4; k.rgba8 = out_rgba8;
-    hipLaunchKernelGGL(kl_composite, dim3((w * h + 255) / 256), dim3(256), 0, c->stream, k, set);
-    if ((e = hipGetLastError()) != hipSuccess) return lhip(c, e, "composite_lights");
-    return VCT_OK;
+    return composite_light_list(c, "composite_lights", pos4, nrm4, alb4, diffuse4, spec4, w, h, lights, n_lights,
+                                CompositeForm{}, out_linear4, out_rgba8);
 }
 
 // Tool / test hooks (not part of the public headers; tools/lights_bench.py, tests): the form

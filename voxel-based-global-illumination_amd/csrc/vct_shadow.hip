@@ -22,7 +22,8 @@
 //               out of a mask -- an AND of compares -- and its loads are sent out of range;
 //               the loop ends when a ballot finds no lane left.  Only alpha is read: 4-byte
 //               loads of the texels' .w, 8 per level at level 0 / isotropic, 24 above.
-//   ks_composite kl_composite (vct_lights.hip) with V read from the vis plane.
+// The composite that reads V is kl_composite<true, *> (vct_lights.hip);
+// vct_composite_shadowed_device here keeps its own rule (vis is required).
 //
 // n <= 512: every level is bound as a buffer resource (base at the first texel's .w), so
 // the spec's zero border is the hardware range check.  n = 1024 (and vct_debug_shadow's
@@ -125,47 +126,6 @@ __global__ void __launch_bounds__(64) ks_march(const ShadowK k, const LightSet s
         const uint32_t ws = wave_sum_u32(steps);
         if (lane == 0 && ws) atomicAdd(k.steps_total, (unsigned long long)ws);
     }
-}
-
-// ---- composite + present with V from the vis plane (kl_composite, vct_lights.hip) -------
-struct CompVK {
-    const float4 *pos, *nrm, *alb, *diff, *spec;
-    const float* vis;
-    int w, h;
-    float g0x, g0y, g0z, inv_h, h2;
-    uint32_t n_lights;
-    float4* lin;
-    uint32_t* rgba8;
-};
-
-__global__ void __launch_bounds__(256) ks_composite(const CompVK k, const LightSet set) {
-    const uint32_t npx = (uint32_t)k.w * (uint32_t)k.h;
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= npx) return;
-    const float4 P = k.pos[i];
-    if (P.w == 0.0f) {   // background: the reference's clear colour
-        if (k.lin) k.lin[i] = make_float4(VCT_CLEAR_R, VCT_CLEAR_G, VCT_CLEAR_B, 0.0f);
-        if (k.rgba8)
-            k.rgba8[i] = (uint32_t)lroundf(VCT_CLEAR_R * 255.0f) | ((uint32_t)lroundf(VCT_CLEAR_G * 255.0f) << 8) |
-                         ((uint32_t)lroundf(VCT_CLEAR_B * 255.0f) << 16) | (255u << 24);
-        return;
-    }
-    const float4 N = k.nrm[i], A = k.alb[i], D = k.diff[i], S = k.spec[i];
-    const float qx = (P.x - k.g0x) * k.inv_h + N.x, qy = (P.y - k.g0y) * k.inv_h + N.y,
-                qz = (P.z - k.g0z) * k.inv_h + N.z;
-    float dr = 0.0f, dg = 0.0f, db = 0.0f;
-    for (uint32_t j = 0; j < k.n_lights; ++j) {
-        const DLight& L = set.l[j];
-        float lx, ly, lz, f, ndl, t_lim;
-        if (!light_terms(L, k.h2, qx, qy, qz, N.x, N.y, N.z, lx, ly, lz, f, ndl, t_lim)) continue;
-        const float vis = k.vis[(size_t)j * npx + i];
-        dr = dr + (((A.x * L.cr) * ndl) * f) * vis;
-        dg = dg + (((A.y * L.cg) * ndl) * f) * vis;
-        db = db + (((A.z * L.cb) * ndl) * f) * vis;
-    }
-    const float fr = (dr + A.x * D.x) + S.x, fg = (dg + A.y * D.y) + S.y, fb = (db + A.z * D.z) + S.z;
-    if (k.lin) k.lin[i] = make_float4(fr, fg, fb, 1.0f);
-    if (k.rgba8) k.rgba8[i] = to8(fr) | (to8(fg) << 8) | (to8(fb) << 16) | (255u << 24);
 }
 
 // ---- host side --------------------------------------------------------------------------
@@ -302,34 +262,14 @@ extern "C" vct_status vct_composite_shadowed_device(vct_ctx* c, const float* pos
                                                     const float* diffuse4, const float* spec4, uint32_t w, uint32_t h,
                                                     const vct_light* lights, uint32_t n_lights, const float* vis,
                                                     float* out_linear4, uint32_t* out_rgba8) {
-    if (!c || !pos4 || !nrm4 || !alb4 || !diffuse4 || !spec4 || w == 0 || h == 0) return VCT_EINVAL;
-    if (!out_linear4 && !out_rgba8) return lfail(c, VCT_EINVAL, "composite: no output");
-    if ((uint64_t)w * h > 0x7fffffffull) return lfail(c, VCT_EINVAL, "composite: frame too large");
-    if (!c->grid.voxelized) return lfail(c, VCT_ESTATE, "composite before voxelize");
-    for (const void* p : {(const void*)pos4, (const void*)nrm4, (const void*)alb4, (const void*)diffuse4,
-                          (const void*)spec4, (const void*)out_linear4})
-        if (((uintptr_t)p & 15u) != 0) return lfail(c, VCT_EINVAL, "composite: float4 buffers must be 16-byte aligned");
-    if (((uintptr_t)out_rgba8 & 3u) != 0) return lfail(c, VCT_EINVAL, "composite: rgba8 buffer must be 4-byte aligned");
+    // vis is needed when a light reads it (a list that is too long is the list check's to report)
+    CompositeForm form;
+    form.vis = vis;
+    form.read_vis = true;
     if (n_lights && n_lights <= VCT_MAX_LIGHTS && (!vis || ((uintptr_t)vis & 3u) != 0))
-        return lfail(c, VCT_EINVAL, "composite_shadowed: vis must be a 4-byte aligned device buffer");
-    LightSet set;
-    std::memset(&set, 0, sizeof set);
-    vct_status st = prepare_list(c, "composite_shadowed", lights, n_lights, set.l);
-    if (st != VCT_OK) return st;
-    hipError_t e = hipSetDevice(c->device);
-    if (e != hipSuccess) return lhip(c, e, "hipSetDevice");
-    const Grid& g = c->grid;
-    CompVK k;
-    k.pos = (const float4*)pos4; k.nrm = (const float4*)nrm4; k.alb = (const float4*)alb4;
-    k.diff = (const float4*)diffuse4; k.spec = (const float4*)spec4;
-    k.vis = vis;
-    k.w = (int)w; k.h = (int)h;
-    k.g0x = g.g0[0]; k.g0y = g.g0[1]; k.g0z = g.g0[2]; k.inv_h = g.inv_h; k.h2 = grid_h2(g);
-    k.n_lights = n_lights;
-    k.lin = (float4*)out_linear4; k.rgba8 = out_rgba8;
-    hipLaunchKernelGGL(ks_composite, dim3((w * h + 255) / 256), dim3(256), 0, c->stream, k, set);
-    if ((e = hipGetLastError()) != hipSuccess) return lhip(c, e, "composite_shadowed");
-    return VCT_OK;
+        form.own_error = "vis must be a 4-byte aligned device buffer";
+    return composite_light_list(c, "composite_shadowed", pos4, nrm4, alb4, diffuse4, spec4, w, h, lights, n_lights, form,
+                                out_linear4, out_rgba8);
 }
 
 // Test hook (not part of the public headers): force64 != 0 sends every grid through the

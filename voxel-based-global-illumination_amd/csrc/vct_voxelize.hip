@@ -21,7 +21,7 @@
 #include <cstring>
 
 #include "vct_internal.h"
-#include "vct_voxel_sat.h"   // the candidate record and range, the scan, the SAT, the bucket table
+#include "vct_voxel_sat.h"   // the triangle setup pieces, the scan, the candidate walk and SAT, the bucket table
 
 #ifdef VCT_DEBUG_WAVES
 // per-wave (start, end, HW_ID | XCC_ID << 32) of the last k2_walk launch (timeline build,
@@ -62,82 +62,39 @@ __global__ void __launch_bounds__(256) k1_tri_setup(
     int* __restrict__ err, uint32_t* __restrict__ maxabs) {
     uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_tri) return;
-    uint32_t vi[3] = {idx[3 * t], idx[3 * t + 1], idx[3 * t + 2]};
     uint32_t m = mat ? mat[t] : 0u;
-    TriGeom g;
-    TriFix f;
     // the material's diffuse map (material_map, vct_voxelize_textured); out of range -> error
     const int32_t tex = (map && m < n_mat) ? map[m] : -1;
-    if (vi[0] >= n_verts || vi[1] >= n_verts || vi[2] >= n_verts || (kd && m >= n_mat) || (map && m >= n_mat) ||
-        tex < -1 || (tex >= 0 && (uint32_t)tex >= n_tex)) {
+    const bool mat_ok = !((kd && m >= n_mat) || (map && m >= n_mat) || tex < -1 || (tex >= 0 && (uint32_t)tex >= n_tex));
+    uint32_t vi[3];
+    float p[3][3], q[3][3];
+    // (an out-of-range index leaves the triangle's mesh_tri entry as it was: the grid is refused)
+    if (!mat_ok || !load_tri(verts, stride, n_verts, idx, t, g0x, g0y, g0z, inv_h, vi, p, q)) {
         atomicOr(err, kK1ErrIndex);
-        g.ext[0] = g.ext[1] = g.ext[2] = 0;
-        counts[t] = 0;
-        geom[t] = g;
+        reject_tri(geom, counts, t);
         return;
     }
     // the K1 input rule (vct_spec.h): Kd outside the fixed-point range is an error, a triangle with
-    // a non-finite q is skipped (NaN fails both compares).  Tested after the vertex loads, so
-    // that all of them are in flight together
+    // a non-finite q is skipped.  Tested after the vertex loads, so that all of them are in
+    // flight together
     const float4 alb = kd ? kd[m] : make_float4(1.0f, 1.0f, 1.0f, 1.0f);
-    float p[3][3], q[3][3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float* src = (const float*)(verts + (size_t)vi[k] * stride);
-        p[k][0] = src[0]; p[k][1] = src[1]; p[k][2] = src[2];
-        q[k][0] = (p[k][0] - g0x) * inv_h;
-        q[k][1] = (p[k][1] - g0y) * inv_h;
-        q[k][2] = (p[k][2] - g0z) * inv_h;
-        g.q[3 * k] = q[k][0]; g.q[3 * k + 1] = q[k][1]; g.q[3 * k + 2] = q[k][2];
-    }
-    // (`&`, not `&&`: short-circuit evaluation would make each load wait for the one before it)
-    const bool kd_ok = (fabsf(alb.x) < VCT_KD_LIMIT) & (fabsf(alb.y) < VCT_KD_LIMIT) & (fabsf(alb.z) < VCT_KD_LIMIT);
-    bool finite = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-        finite &= (fabsf(q[k][0]) < __builtin_inff()) & (fabsf(q[k][1]) < __builtin_inff()) &
-                  (fabsf(q[k][2]) < __builtin_inff());
-    if (!kd_ok || !finite) {   // no candidates, nothing for max|value|, a zero triangle for the G-buffer passes
+    const bool kd_ok = kd_legal(alb.x, alb.y, alb.z);
+    if (!kd_ok || !tri_finite(q)) {   // no candidates, nothing for max|value|, a zero triangle for the G-buffer passes
         if (!kd_ok) atomicOr(err, kK1ErrKd);
-        g.lo[0] = g.lo[1] = g.lo[2] = 0;
-        g.ext[0] = g.ext[1] = g.ext[2] = 0;
-        g.pad = 0;
-        geom[t] = g;
-        counts[t] = 0;
+        reject_tri(geom, counts, t);
+        const float z[3] = {0.0f, 0.0f, 0.0f};
+        store_mesh_tri(mesh_tri, t, z, z, z, alb, -1);
         const float4 z4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        mesh_tri[4 * t + 0] = z4;
-        mesh_tri[4 * t + 1] = z4;
-        mesh_tri[4 * t + 2] = z4;
-        mesh_tri[4 * t + 3] = make_float4(alb.x, alb.y, alb.z, __int_as_float(-1));
         if (tex >= 0) { mesh_uv[2 * t + 0] = z4; mesh_uv[2 * t + 1] = z4; }
         return;
     }
-    float e1[3] = {p[1][0] - p[0][0], p[1][1] - p[0][1], p[1][2] - p[0][2]};
-    float e2[3] = {p[2][0] - p[0][0], p[2][1] - p[0][1], p[2][2] - p[0][2]};
-    float fn[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2],
-                   e1[0] * e2[1] - e1[1] * e2[0]};
-    float len = sqrtf(dot3(fn[0], fn[1], fn[2], fn[0], fn[1], fn[2]));
-    if (len > 0.0f) { fn[0] = fn[0] / len; fn[1] = fn[1] / len; fn[2] = fn[2] / len; }
-    else { fn[0] = 0.0f; fn[1] = 0.0f; fn[2] = 0.0f; }
-    f.fix[0] = (long long)roundf(alb.x * VCT_FIXED_ONE);
-    f.fix[1] = (long long)roundf(alb.y * VCT_FIXED_ONE);
-    f.fix[2] = (long long)roundf(alb.z * VCT_FIXED_ONE);
-    f.fix[3] = (long long)roundf(fn[0] * VCT_FIXED_ONE);
-    f.fix[4] = (long long)roundf(fn[1] * VCT_FIXED_ONE);
-    f.fix[5] = (long long)roundf(fn[2] * VCT_FIXED_ONE);
+    TriGeom g;
+    TriFix f;
+    float e1[3], e2[3];
+    face_fix(p, alb, f.fix, e1, e2);
     f.tex = tex;
     f.pad = 0;
-    {   // the largest |fixed-point value| a hit of this triangle adds (a textured albedo
-        // Kd x T with T <= 1 rounds to at most Kd's); clamped at 2^31
-        unsigned long long mx = 0;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const unsigned long long a = (unsigned long long)(f.fix[i] < 0 ? -f.fix[i] : f.fix[i]);
-            mx = a > mx ? a : mx;
-        }
-        const uint32_t m32 = mx >= (1ull << 31) ? (1u << 31) : (uint32_t)mx;
-        if (m32 > __hip_atomic_load(maxabs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(maxabs, m32);
-    }
+    fix_maxabs(f.fix, maxabs);
     if (tex >= 0) {
         TriUV r;
 #pragma unroll
@@ -152,24 +109,10 @@ __global__ void __launch_bounds__(256) k1_tri_setup(
         mesh_uv[2 * t + 0] = make_float4(r.uv[0], r.uv[1], r.uv[2], r.uv[3]);
         mesh_uv[2 * t + 1] = make_float4(r.uv[4], r.uv[5], 0.0f, 0.0f);
     }
-    unsigned long long cnt = 1;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        int lo, hi;
-        cand_range(fmin3(q[0][a], q[1][a], q[2][a]), fmax3(q[0][a], q[1][a], q[2][a]), n, lo, hi);
-        g.lo[a] = lo;
-        g.ext[a] = hi >= lo ? (uint32_t)(hi - lo + 1) : 0u;
-        cnt *= g.ext[a];
-    }
-    g.pad = 0;
+    counts[t] = tri_range(q, n, g);
     geom[t] = g;
     fixo[t] = f;
-    counts[t] = cnt;
-    // keep the triangle for the G-buffer ray caster (world units)
-    mesh_tri[4 * t + 0] = make_float4(p[0][0], p[0][1], p[0][2], 0.0f);
-    mesh_tri[4 * t + 1] = make_float4(e1[0], e1[1], e1[2], 0.0f);
-    mesh_tri[4 * t + 2] = make_float4(e2[0], e2[1], e2[2], 0.0f);
-    mesh_tri[4 * t + 3] = make_float4(alb.x, alb.y, alb.z, __int_as_float(tex));
+    store_mesh_tri(mesh_tri, t, p[0], e1, e2, alb, tex);   // kept for the G-buffer ray caster
 }
 
 // one lane = kCandPerThread consecutive (triangle, voxel) candidates.  PACKED: a hit adds
@@ -191,33 +134,9 @@ __global__ void __launch_bounds__(256) k1_candidates(const TriGeom* __restrict__
     const unsigned long long total = *total_p;
     const unsigned long long c0 = ((unsigned long long)blockIdx.x * blockDim.x + threadIdx.x) * kCandPerThread;
     if (c0 >= total) return;
-    // upper_bound(offs, c0) - 1, searched between the triangles of this bucket's start
-    // and the next bucket's start (a few steps instead of log2(n_tri) dependent loads)
-    const unsigned long long bk = c0 / kCandBucket, nbk = (total + kCandBucket - 1) / kCandBucket;
-    uint32_t lo = starts[bk], hi = bk + 1 < nbk ? starts[bk + 1] + 1 : n_tri;
-    while (hi - lo > 1) {
-        uint32_t mid = (lo + hi) >> 1;
-        if (offs[mid] <= c0) lo = mid; else hi = mid;
-    }
-    uint32_t t = lo;
-    while (t + 1 < n_tri && offs[t + 1] <= c0) ++t;  // skip zero-count triangles
-    unsigned long long next = t + 1 < n_tri ? offs[t + 1] : total;
-    for (int k = 0; k < kCandPerThread; ++k) {
-        const unsigned long long c = c0 + k;
-        if (c >= total) break;
-        while (c >= next) { ++t; next = t + 1 < n_tri ? offs[t + 1] : total; }
-        const TriGeom& g = geom[t];
-        unsigned long long local = c - offs[t];
-        uint32_t ex = g.ext[0], ey = g.ext[1];
-        uint32_t x = (uint32_t)(local % ex);
-        unsigned long long r = local / ex;
-        uint32_t y = (uint32_t)(r % ey);
-        uint32_t z = (uint32_t)(r / ey);
-        int vx = g.lo[0] + (int)x, vy = g.lo[1] + (int)y, vz = g.lo[2] + (int)z;
-        float q[9];
-#pragma unroll
-        for (int i = 0; i < 9; ++i) q[i] = g.q[i];
-        if (!tri_box_overlap(q, (float)vx + 0.5f, (float)vy + 0.5f, (float)vz + 0.5f)) continue;
+    const uint32_t t0 = find_tri_bucketed(offs, starts, n_tri, total, c0);
+    for_each_hit<kCandPerThread>(geom, offs, n_tri, total, c0, t0,
+                                 [&](uint32_t t, int vx, int vy, int vz, const float* q) __attribute__((always_inline)) {
         size_t v = (size_t)vx + (size_t)n * ((size_t)vy + (size_t)n * (size_t)vz);
         unsigned long long* a = (unsigned long long*)(accum + 8 * v);
         const TriFix& f = fixr[t];
@@ -243,7 +162,7 @@ __global__ void __launch_bounds__(256) k1_candidates(const TriGeom* __restrict__
             for (int i = 3; i < 6; ++i) atomicAdd(a + i, (unsigned long long)f.fix[i]);
         }
         if (atomicAdd(a + (PACKED ? 3 : 6), 1ull) == 0ull) atomicOr(occ_bits + (v >> 6), 1ull << (v & 63));   // first hit
-    }
+    });
 }
 
 // Sparse reset before a voxelization: the records, voxels and level-0 texels of
@@ -535,28 +454,16 @@ hipError_t voxelize_pass(vct_ctx* c, const void* d_verts, uint32_t stride, uint3
     hipStream_t s = c->stream;
     const size_t nv = (size_t)g.n * g.n * g.n;
     hipError_t e;
-    // scratch layout: geom | fix | counts | offsets | tile sums | total, max|value| |
-    // textured triangles' UVs
-    const uint32_t n_tiles = (n_tri + kScanTile - 1) / kScanTile;
-    size_t off_geom = 0;
-    size_t off_fix = off_geom + sizeof(TriGeom) * (size_t)n_tri;
-    size_t off_cnt = off_fix + sizeof(TriFix) * (size_t)n_tri;
-    size_t off_offs = off_cnt + 8 * (size_t)n_tri;
-    size_t off_tiles = off_offs + 8 * (size_t)n_tri;
-    size_t off_total = off_tiles + 8 * (size_t)(n_tiles + 1);
-    size_t off_uv = (off_total + 64 + 255) & ~(size_t)255;
-    size_t bytes = off_uv + (d_map ? sizeof(TriUV) * (size_t)n_tri : 0);   // (the bucket table: scratch 7)
-    void* sp;
-    if ((e = scratch_get(c, 1, bytes, &sp)) != hipSuccess) return e;
-    char* base = (char*)sp;
-    TriGeom* geom = (TriGeom*)(base + off_geom);
-    TriFix* fix = (TriFix*)(base + off_fix);
-    unsigned long long* cnt = (unsigned long long*)(base + off_cnt);
-    unsigned long long* offs = (unsigned long long*)(base + off_offs);
-    unsigned long long* tiles = (unsigned long long*)(base + off_tiles);
-    unsigned long long* total = (unsigned long long*)(base + off_total);
-    uint32_t* maxabs = (uint32_t*)(base + off_total + 8);
-    TriUV* tuv = d_map ? (TriUV*)(base + off_uv) : nullptr;
+    // the head: total, max|value|; the tail: the textured triangles' UVs
+    TriTemps tt;
+    if ((e = tri_temps(c, n_tri, sizeof(TriFix), d_map ? sizeof(TriUV) * (size_t)n_tri : 0, tt)) != hipSuccess) return e;
+    TriGeom* geom = tt.geom;
+    TriFix* fix = (TriFix*)tt.fix;
+    unsigned long long* cnt = tt.counts;
+    unsigned long long* offs = tt.offs;
+    unsigned long long* total = (unsigned long long*)tt.head;
+    uint32_t* maxabs = (uint32_t*)(total + 1);
+    TriUV* tuv = d_map ? (TriUV*)tt.tail : nullptr;
 
     // sparse reset of the previous voxelization (its occupied list), then the bits
     const size_t nwords = nv / 64;
@@ -573,9 +480,7 @@ hipError_t voxelize_pass(vct_ctx* c, const void* d_verts, uint32_t stride, uint3
                            (const char*)d_verts, stride, n_verts, d_idx, n_tri, d_mat, d_kd, n_mat, d_map,
                            uv_offset, c->tex.n, (int)g.n, g.g0[0], g.g0[1], g.g0[2], g.inv_h, geom, fix, tuv, cnt,
                            c->mesh.tri, c->mesh.uv, d_err, maxabs);
-        hipLaunchKernelGGL(k_scan_tiles, dim3(n_tiles), dim3(kScanBlock), 0, s, cnt, offs, tiles, n_tri);
-        hipLaunchKernelGGL(k_scan_carry, dim3(1), dim3(kScanBlock), 0, s, tiles, n_tiles, total);
-        hipLaunchKernelGGL(k_scan_add, dim3(n_tiles), dim3(kScanBlock), 0, s, offs, tiles, n_tri);
+        launch_count_scan(s, cnt, offs, tt.tiles, n_tri, total);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         // the candidate total is only known on the device: read it back to size the grid
         // (with the largest |value| a hit adds)
@@ -591,21 +496,15 @@ hipError_t voxelize_pass(vct_ctx* c, const void* d_verts, uint32_t stride, uint3
         const unsigned long long safe = h_maxabs ? ((1ull << 31) - 1) / h_maxabs : ~0ull;
         use_packed = packed && safe >= 256;
         if (h_total > 0) {
-            unsigned long long threads = (h_total + kCandPerThread - 1) / kCandPerThread;
-            unsigned long long blocks = (threads + 255) / 256;
-            if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-            const unsigned long long nbk = (h_total + kCandBucket - 1) / kCandBucket;
-            void* bp;
-            if ((e = scratch_get(c, 7, (size_t)nbk * 4, &bp)) != hipSuccess) return e;
-            uint32_t* starts = (uint32_t*)bp;
-            hipLaunchKernelGGL(k1_bucket_starts, dim3((n_tri + 255) / 256), dim3(256), 0, s, offs, n_tri, total,
-                               starts);
+            uint32_t blocks;
+            uint32_t* starts;
+            if ((e = launch_bucket_starts(c, offs, n_tri, total, h_total, &blocks, &starts)) != hipSuccess) return e;
             if (use_packed)
-                hipLaunchKernelGGL(k1_candidates<true>, dim3((uint32_t)blocks), dim3(256), 0, s, geom, fix, offs,
+                hipLaunchKernelGGL(k1_candidates<true>, dim3(blocks), dim3(256), 0, s, geom, fix, offs,
                                    n_tri, total, (int)g.n, g.accum, g.occ_bits, starts, tuv, c->tex.texels,
                                    c->tex.desc);
             else
-                hipLaunchKernelGGL(k1_candidates<false>, dim3((uint32_t)blocks), dim3(256), 0, s, geom, fix, offs,
+                hipLaunchKernelGGL(k1_candidates<false>, dim3(blocks), dim3(256), 0, s, geom, fix, offs,
                                    n_tri, total, (int)g.n, g.accum, g.occ_bits, starts, tuv, c->tex.texels,
                                    c->tex.desc);
         }
