@@ -324,7 +324,11 @@ vct_status vct_comm_frame_layout(uint32_t width, uint32_t height, uint32_t nrank
 /* ---- G-buffer (input producer) -----------------------
  * Ray-casts the triangles of the last vct_voxelize call through `cam` into a
  * device G-buffer (pos4.w = 1 on hit, 0 on background).  Normals are the face
- * normals turned toward the viewer; albedo = material Kd; alb4.w = roughness. */
+ * normals turned toward the viewer; albedo = material Kd; alb4.w = roughness.
+ * Camera and frame size follow the "G-buffer input rule" of vct_spec.h (finite
+ * position, orthonormal front / up / right, zoom_deg, near / far, width / height and
+ * the focal-length bound); anything else is VCT_EINVAL with nothing written.  The
+ * hit is the nearest t > 0 over all triangles, then tested against near / far. */
 vct_status vct_gbuffer_raycast_device(vct_ctx* ctx, const vct_camera* cam, uint32_t width,
                                       uint32_t height, float roughness, float* pos4,
                                       float* nrm4, float* alb4);

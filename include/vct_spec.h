@@ -141,6 +141,43 @@
  *    VCT_COLOR_LIMIT = 2^127 / (VCT_KD_LIMIT * 2 * VCT_MAX_LIGHTS) = 2^105. */
 #define VCT_COLOR_LIMIT     4.05648192e31f   /* 2^105 exactly */
 
+/* G-buffer input rule (what a camera, a frame size and a mesh mean to vct_gbuffer_raycast_device
+ * and vct_gbuffer_raster_device; one rule for both calls; every implementation restates it):
+ *  Definition: the brute-force caster defines the result.  Per pixel (x, y), row 0 = top:
+ *      tan_half = tanf(zoom_deg * 0.5f * 3.14159265358979f / 180.0f), aspect = (float)w / (float)h
+ *      ndx = (2 * (x + 0.5f) / w - 1) * tan_half * aspect,  ndy = (1 - 2 * (y + 0.5f) / h) * tan_half
+ *      D = front + ndx * right + ndy * up,  d = D * (1.0f / sqrtf(dot3(D, D)))
+ *    The binned pass returns the same three planes bit for bit on every legal input.
+ *  Hit selection: t_k = the Moller-Trumbore parameter of triangle k (|det| < 1e-12f, u < 0,
+ *    u > 1, v < 0 or u + v > 1 is a miss).  The hit is the smallest t_k > 0 over ALL triangles,
+ *    the lower index on equal t.  Only then depth = t * dot3(d, front) is tested: the pixel is
+ *    background if there is no hit, depth < near_plane or depth > far_plane.  A hit nearer
+ *    than near_plane (or farther than far_plane) therefore hides what lies behind it; it is
+ *    not skipped in favour of the next one.
+ *  Camera (anything else is VCT_EINVAL, with nothing written to the three planes):
+ *    position: three finite floats.
+ *    front, up, right: finite, and orthonormal to VCT_GBUF_ORTHO_EPS = 2^-20: with the dot
+ *      products taken in double, |a.a - 1| <= eps for each of the three and |a.b| <= eps for
+ *      each of the three pairs.  Handedness is not tested (a mirrored basis mirrors the frame).
+ *      A vct.camera.Camera (float64-normalised, rounded to float32) is within 1.1e-7 and the
+ *      float32 GLM camera of the host within 2.3e-7 at every yaw and pitch.
+ *    zoom_deg: VCT_GBUF_ZOOM_MIN < zoom_deg < VCT_GBUF_ZOOM_MAX (2^-10 and 179 degrees; NaN
+ *      fails both), so tan_half is finite and positive.
+ *    near_plane, far_plane: finite, 0 <= near_plane <= far_plane (equal is legal).
+ *    w, h: 1 <= w, h <= VCT_GBUF_MAX_DIM = 2^14 each (at most 2^20 bins and 2^28 pixels).
+ *    focal length: with s = h / (2 tan_half) (pixels per unit of tangent, the same on both
+ *      axes) and M = 1 + tan_half * (1 + w / h) (a bound of |D|), in double from the float
+ *      tan_half:  s * M * M <= VCT_GBUF_FOCAL_LIMIT = 2^17.  This is what keeps the float32
+ *      projection of the binned pass within a quarter of a pixel.
+ *  Triangles are device data, never a status: any finite vertices (1e18 included), zero-area
+ *    triangles and the all-zero record of a K1-skipped triangle ("K1 input rule") do what the
+ *    Moller-Trumbore test above says in float32; an all-zero record is never hit. */
+#define VCT_GBUF_ORTHO_EPS    9.5367431640625e-07   /* 2^-20 (double)  */
+#define VCT_GBUF_ZOOM_MIN     0.0009765625f         /* 2^-10 degrees   */
+#define VCT_GBUF_ZOOM_MAX     179.0f
+#define VCT_GBUF_MAX_DIM      16384u                /* 2^14            */
+#define VCT_GBUF_FOCAL_LIMIT  131072.0              /* 2^17 (double)   */
+
 /* ---- diffuse maps (albedo = Kd x diffuse map; SURVEY 8a Model::loadMaterials) --
  * The reference loads a material's map_Kd with stbi_load(path, .., 0), uploads it
  * as glTexImage2D(GL_RED | GL_RGB | GL_RGBA, GL_UNSIGNED_BYTE) and samples it with

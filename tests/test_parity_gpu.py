@@ -766,6 +766,26 @@ def test_raycast_matches_numpy(gpu_ready):
     same_n = np.all(np.abs(nrm.cpu().numpy()[both] - rn[both]) < 1e-3, axis=-1).mean()
     assert same_n > 0.99
     assert np.abs(gp[both][:, :3] - rp[both][:, :3]).max() < 1e-3
+    # ... and exactly, where float32 rounding cannot decide (tests/gbuffer_ref.py: the float64
+    # caster's robust pixels): the same validity, the winner's own Kd, its plane and its normal
+    import gbuffer_ref as GR
+    from gbuffer_inputs import Cam
+    v, i, m, k = arrs
+    rec = GR.tri_records(v, i)
+    ref = GR.cast64(rec, Cam(cam.position, cam.front, cam.up, cam.right, cam.zoom, cam.near, cam.far), w, h)
+    rob = GR.robust(ref, 1e-4)
+    assert rob.mean() >= 0.9
+    assert np.array_equal(gp[..., 3][rob] != 0, ref["valid"][rob])
+    sel = rob & ref["valid"]
+    win = ref["hit"][sel]
+    assert sel.sum() > 0.2 * w * h
+    assert np.array_equal(alb.cpu().numpy()[sel][:, :3], k[m[win], :3])
+    nf = np.cross(rec[win, 1].astype(np.float64), rec[win, 2].astype(np.float64))
+    nf /= np.linalg.norm(nf, axis=1, keepdims=True)
+    off = np.einsum("ij,ij->i", gp[sel][:, :3].astype(np.float64) - rec[win, 0], nf)
+    assert np.abs(off).max() < 1e-5
+    gn = nrm.cpu().numpy()[sel][:, :3].astype(np.float64)
+    assert np.abs(np.abs(np.einsum("ij,ij->i", gn, nf)) - 1.0).max() < 1e-5
     ctx.close()
 
 

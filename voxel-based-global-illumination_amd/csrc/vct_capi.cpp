@@ -7,6 +7,7 @@
 // No exception crosses the ABI.  There is no CPU fallback: without a HIP device
 // vct_create fails with VCT_EDEVICE.
 #include <hip/hip_runtime.h>
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -869,9 +870,38 @@ uint32_t vct_tile_offset(uint32_t w, uint32_t h, uint32_t rank, uint32_t world) 
     return rank * q + (rank < rem ? rank : rem);
 }
 
+/* the "G-buffer input rule" of vct_spec.h (camera and frame size; one rule for both passes) */
+static const char* bad_gbuffer_input(const vct_camera* cam, uint32_t w, uint32_t h) {
+    if (w == 0 || h == 0 || w > VCT_GBUF_MAX_DIM || h > VCT_GBUF_MAX_DIM)
+        return "gbuffer: frame size outside 1..VCT_GBUF_MAX_DIM";
+    const float* b[3] = {cam->front, cam->up, cam->right};
+    for (int k = 0; k < 3; ++k)
+        if (!(fabsf(cam->position[k]) <= FLT_MAX)) return "gbuffer: non-finite camera position";
+    for (int i = 0; i < 3; ++i)
+        for (int k = 0; k < 3; ++k)
+            if (!(fabsf(b[i][k]) <= FLT_MAX)) return "gbuffer: non-finite camera basis";
+    for (int i = 0; i < 3; ++i)
+        for (int j = i; j < 3; ++j) {
+            const double g = ((double)b[i][0] * b[j][0] + (double)b[i][1] * b[j][1]) + (double)b[i][2] * b[j][2];
+            if (!(fabs(g - (i == j ? 1.0 : 0.0)) <= VCT_GBUF_ORTHO_EPS))
+                return "gbuffer: front / up / right not orthonormal to VCT_GBUF_ORTHO_EPS";
+        }
+    if (!(cam->zoom_deg > VCT_GBUF_ZOOM_MIN && cam->zoom_deg < VCT_GBUF_ZOOM_MAX))
+        return "gbuffer: zoom_deg outside (VCT_GBUF_ZOOM_MIN, VCT_GBUF_ZOOM_MAX)";
+    if (!(fabsf(cam->near_plane) <= FLT_MAX && fabsf(cam->far_plane) <= FLT_MAX && cam->near_plane >= 0.0f &&
+          cam->near_plane <= cam->far_plane))
+        return "gbuffer: near / far not finite with 0 <= near <= far";
+    const float tan_half = tanf(cam->zoom_deg * 0.5f * 3.14159265358979f / 180.0f);
+    const double s = 0.5 * (double)h / (double)tan_half;
+    const double m = 1.0 + (double)tan_half * (1.0 + (double)w / (double)h);
+    if (!(s * m * m <= VCT_GBUF_FOCAL_LIMIT)) return "gbuffer: focal length above VCT_GBUF_FOCAL_LIMIT";
+    return nullptr;
+}
+
 vct_status vct_gbuffer_raycast_device(vct_ctx* c, const vct_camera* cam, uint32_t w, uint32_t h,
                                       float rough, float* pos4, float* nrm4, float* alb4) {
-    if (!c || !cam || !pos4 || !nrm4 || !alb4 || w == 0 || h == 0) return VCT_EINVAL;
+    if (!c || !cam || !pos4 || !nrm4 || !alb4) return VCT_EINVAL;
+    if (const char* bad = bad_gbuffer_input(cam, w, h)) return fail(c, VCT_EINVAL, bad);
     if (!c->mesh.tri) return fail(c, VCT_ESTATE, "raycast before voxelize");
     vct_status st = use_device(c);
     if (st != VCT_OK) return st;
@@ -881,9 +911,8 @@ vct_status vct_gbuffer_raycast_device(vct_ctx* c, const vct_camera* cam, uint32_
 
 vct_status vct_gbuffer_raster_device(vct_ctx* c, const vct_camera* cam, uint32_t w, uint32_t h, float rough,
                                      float* pos4, float* nrm4, float* alb4) {
-    if (!c || !cam || !pos4 || !nrm4 || !alb4 || w == 0 || h == 0) return VCT_EINVAL;
-    if ((uint64_t)w * h > 0x7fffffffull || (uint64_t)((w + 15) / 16) * ((h + 15) / 16) > (1u << 20))
-        return fail(c, VCT_EINVAL, "raster: frame too large");
+    if (!c || !cam || !pos4 || !nrm4 || !alb4) return VCT_EINVAL;
+    if (const char* bad = bad_gbuffer_input(cam, w, h)) return fail(c, VCT_EINVAL, bad);
     if (!c->mesh.tri) return fail(c, VCT_ESTATE, "raster before voxelize");
     vct_status st = use_device(c);
     if (st != VCT_OK) return st;

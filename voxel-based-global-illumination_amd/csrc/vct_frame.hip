@@ -150,16 +150,24 @@ __global__ void __launch_bounds__(256) k_raycast(RayK k) {
 
 // ---- tile-binned G-buffer pass ------------------------
 // Screen-space binning of the triangles into 16x16-pixel tiles (projected
-// through the reference camera; clipped to cz >= 1e-5 so the bounding boxes are
+// through the reference camera; clipped to cz >= kZc so the bounding boxes are
 // conservative), then one workgroup per tile intersects its pixels' rays with
 // the tile's triangles only.  Ties in t go to the lower triangle index, so the
 // result equals the brute-force caster's bit for bit, at O(px x tris per tile).
+// The caster takes the nearest t > 0 over all triangles before it looks at the
+// depth (vct_spec.h "G-buffer input rule"), so a tile's bin must hold every
+// triangle a ray of the tile can hit at any depth: nothing is culled against
+// far_plane, a triangle that can be hit nearer than kZc gets the whole frame, and
+// a box grows with the triangle's conditioning (an edge-on one: the whole frame).
 constexpr int kGT = 16;
+constexpr float kZc = 1e-5f;
 
 struct BinK {
     RayK r;
     int tiles_x, tiles_y;
     float sxs, sys;                // pixel scale: X = w/2 + (cx/cz) sxs, Y = h/2 - (cy/cz) sys
+    float t_near;                  // 2 kZc max|D|: a hit with cz < kZc has a ray parameter below half of this
+    float pad;                     // 2^-20 s M^2: pixels of float32 slack per unit of a triangle's conditioning
     int4* rect;                    // per triangle tile rectangle (x0 > x1: culled)
     uint32_t* count;               // per tile: triangles, then the fill cursor
     uint32_t* offset;              // per tile: exclusive prefix of count; [n_tiles] = total
@@ -181,14 +189,14 @@ __global__ void __launch_bounds__(256) k_bin_rect(BinK k) {
         c[i][2] = dot3(qx, qy, qz, r.fx, r.fy, r.fz);
     }
     // clip the triangle to cz >= zc (Sutherland-Hodgman, one plane), project the polygon
-    const float zc = 1e-5f;
+    const float zc = kZc;
     float lo_x = __builtin_inff(), lo_y = __builtin_inff(), hi_x = -__builtin_inff(), hi_y = -__builtin_inff();
-    bool any = false, beyond = true;
+    bool any = false, below = false;
     for (int i = 0; i < 3; ++i) {
         const float* a = c[i];
         const float* b = c[(i + 1) % 3];
-        beyond &= a[2] > r.far_p;
         const bool ina = a[2] >= zc, inb = b[2] >= zc;
+        below |= !ina;
         float p[2][3];
         int np = 0;
         if (ina) { p[np][0] = a[0]; p[np][1] = a[1]; p[np][2] = a[2]; ++np; }
@@ -203,11 +211,33 @@ __global__ void __launch_bounds__(256) k_bin_rect(BinK k) {
             any = true;
         }
     }
+    // How far from its projected box float32 lets the caster still report a hit: the rounding of
+    // u and v moves the silhouette by about 2^-22 s M^2 cond pixels, cond = max(|v0 - eye|, |e1|,
+    // |e2|) |e1| |e2| / |(v0 - eye) . n| >= 1 (a triangle seen edge-on has no bound).  pad is
+    // 2^-20 s M^2 <= 1/8 (vct_spec.h VCT_GBUF_FOCAL_LIMIT); grow widens the one-pixel margin.
+    // Zero area, overflow or NaN: the whole frame.
+    // (an edge of exact zeros is never hit: det is 0 or NaN for every ray)
+    const bool edges = (e1.x != 0.0f || e1.y != 0.0f || e1.z != 0.0f) && (e2.x != 0.0f || e2.y != 0.0f || e2.z != 0.0f);
+    const float l1 = sqrtf(dot3(e1.x, e1.y, e1.z, e1.x, e1.y, e1.z)), l2 = sqrtf(dot3(e2.x, e2.y, e2.z, e2.x, e2.y, e2.z));
+    const float nx = e1.y * e2.z - e1.z * e2.y, ny = e1.z * e2.x - e1.x * e2.z, nz = e1.x * e2.y - e1.y * e2.x;
+    const float tx = v0.x - r.px, ty = v0.y - r.py, tz = v0.z - r.pz;
+    const float dn = fabsf(dot3(tx, ty, tz, nx, ny, nz)), nl = sqrtf(dot3(nx, ny, nz, nx, ny, nz));
+    const float lt = sqrtf(dot3(tx, ty, tz, tx, ty, tz));
+    const float grow = k.pad * (fmaxf(lt, fmaxf(l1, l2)) * (l1 * l2) / dn);
+    bool full = !(grow < 32768.0f);   // NaN too; no legal frame is wider
+    // A triangle with a vertex under zc may be hit at 0 < cz < zc, anywhere on the screen, but
+    // only by a ray parameter below t_near / 2, so only if its plane passes that near the eye.
+    // It keeps the clipped box when the plane is provably farther than t_near: the rounding of
+    // dn and of |n| is below 2^-20 (|v0 - eye| + t_near) |e1| |e2| while |n| is a normal number.
+    if (below) full |= !(nl > 1e-30f && dn > k.t_near * nl + 9.5367431640625e-07f * (lt + k.t_near) * (l1 * l2));
     int4 rc = make_int4(1, 0, 0, 0);   // culled
-    if (any && !beyond) {
-        // one pixel of margin, pixel centres at +0.5
-        const float x0 = fmaxf(lo_x - 1.5f, 0.0f), x1 = fminf(hi_x + 0.5f, (float)(r.w - 1));
-        const float y0 = fmaxf(lo_y - 1.5f, 0.0f), y1 = fminf(hi_y + 0.5f, (float)(r.h - 1));
+    if (!edges) {
+    } else if (full) {
+        rc = make_int4(0, 0, k.tiles_x - 1, k.tiles_y - 1);
+    } else if (any) {
+        // one pixel of margin and grow, pixel centres at +0.5
+        const float x0 = fmaxf(lo_x - 1.5f - grow, 0.0f), x1 = fminf(hi_x + 0.5f + grow, (float)(r.w - 1));
+        const float y0 = fmaxf(lo_y - 1.5f - grow, 0.0f), y1 = fminf(hi_y + 0.5f + grow, (float)(r.h - 1));
         if (x0 <= x1 && y0 <= y1)
             rc = make_int4((int)x0 / kGT, (int)y0 / kGT, (int)x1 / kGT, (int)y1 / kGT);
     }
@@ -398,6 +428,10 @@ hipError_t launch_gbuffer_binned(vct_ctx* c, const vct_camera* cam, uint32_t w, 
     k.tiles_y = (int)((h + kGT - 1) / kGT);
     k.sxs = 0.5f * (float)w / (k.r.tan_half * k.r.aspect);
     k.sys = 0.5f * (float)h / k.r.tan_half;
+    const float ext = k.r.tan_half * k.r.aspect;
+    k.t_near = 2.0f * kZc * sqrtf(1.0f + ext * ext + k.r.tan_half * k.r.tan_half);
+    const float reach = 1.0f + k.r.tan_half + ext;
+    k.pad = 9.5367431640625e-07f * k.sys * reach * reach;
     const uint32_t n_tiles = (uint32_t)(k.tiles_x * k.tiles_y), n_tri = c->mesh.n_tri;
     const size_t b_rect = ((size_t)n_tri * sizeof(int4) + 255) & ~(size_t)255;
     const size_t b_cnt = ((size_t)n_tiles * 4 + 255) & ~(size_t)255;
