@@ -44,6 +44,11 @@ const char* vcth_texture_error(const vcth_model* m, uint32_t i);
  * w * comp bytes (release with vcth_free_image).  Returns 0, or -1 with a message. */
 int vcth_decode_png(const uint8_t* file, size_t bytes, uint8_t** data, uint32_t* width, uint32_t* height, int* comp,
                     char* err, int errlen);
+/* PNG encode, the way back (the headless host writes its voxel view with it): h rows of w * comp
+ * bytes, comp 1..4, 8 bits per channel -> *file, *file_bytes (release with vcth_free_image).
+ * vcth_decode_png reads it back unchanged.  Returns 0, or -1 with a message. */
+int vcth_encode_png(const uint8_t* data, uint32_t width, uint32_t height, int comp, uint8_t** file, size_t* file_bytes,
+                    char* err, int errlen);
 void vcth_free_image(uint8_t* data);
 void vcth_free(vcth_model* m);
 /* Apply a column-major 4x4 model matrix to every vertex position (host Model::Transform). */

@@ -223,6 +223,13 @@
 #define VCT_CLEAR_G         0.3f
 #define VCT_CLEAR_B         0.3f
 #define VCT_INV_GAMMA       0.454545468f /* 1 / 2.2 */
+/* The voxel view ("voxel view", below) presents through the same step.  Its shade: the hit
+ * cell's colour times one literal per entry-face axis, so cubes read as cubes; and the cap of
+ * its walk, in steps per cell of an axis. */
+#define VCT_VOXVIEW_SHADE_X        0.8f
+#define VCT_VOXVIEW_SHADE_Y        1.0f
+#define VCT_VOXVIEW_SHADE_Z        0.6f
+#define VCT_VOXVIEW_STEPS_PER_CELL 3
 
 /* ---- light bounces (vct_inject_bounces, include/vct_bounce.h; no new literals) ------
  * L0 = the level-0 radiance at the call (K2's output), A / N = K1's resolved albedo and
@@ -739,5 +746,82 @@
  *    W > 0:  out4 = (V.r / W, V.g / W, V.b / W, 1.0f - V.a / W);  otherwise (W = 0, or a NaN)
  *    out4 = (+0, +0, +0, 1.0f) and the point is a miss.  A background point (pos.w == 0, -0 too)
  *    gets +0 in all four channels and is no miss. */
+
+/* ---- voxel view (vct_voxel_pick_device / vct_voxel_view_device, include/vct_voxview.h;
+ *      tests/voxview_ref.py restates it) ---------------------------------------------------------
+ *  All arithmetic is float32, one rounding per operation, no contraction; the fused operations
+ *    are the fmaf() calls named here.  A ray is (org, v, t_lim); the launch has a level l with
+ *    n_l = n >> l cells per axis, nf = (float)n_l, and a solid source.
+ *  Ray of a pick: org = org4.xyz, v = dir4.xyz, t_lim = dir4.w.  Ray of view pixel (x, y):
+ *    org = cam->position, v = the d of the "G-buffer input rule" (vct_view.h pixel_ray, already
+ *    normalised there, and normalised once more below like any other v), t_lim = +inf.
+ *  Origin:  o_c = (org_c - g0_c) * inv_h  (the fog rays' expression; the view evaluates it once on
+ *    the host),  ol_c = o_c * 2^-l  (exact).
+ *  Direction (the K2 direction rule):  len = sqrtf(dot3(v, v)),  d_c = v_c / len.
+ *  Limit:  lim = t_lim, or +inf when t_lim is a NaN;  ll = lim * 2^-l  (exact).
+ *  Not a ray -- len not finite or not > 0, or a non-finite component of o or of d: a miss with
+ *    0 steps.  (A non-finite ol has a non-finite o; !(ll > 0) is an empty segment below.)
+ *  Slab: "volumetric fog"'s, per axis c with nf, ol and len = ll:  inv = 1.0f / d_c;  an axis with
+ *    d_c == 0 or inv not finite does not clip when 0 <= ol_c <= nf and empties the segment
+ *    otherwise; else ta = (0.0f - ol_c) * inv, tb = (nf - ol_c) * inv, tn_c = fminf(ta, tb),
+ *    tf_c = fmaxf(ta, tb);  t0 = the largest of 0 and the clipping axes' tn_c,  t1 = the smallest
+ *    of ll and their tf_c;  the segment is empty unless ll > 0 and t1 > t0.  An empty segment is a
+ *    miss with 0 steps.
+ *    t0 also names its axis:  t0 = +0, a0 = none;  then for c = x, y, z in turn, if the axis clips
+ *    and tn_c > t0:  t0 = tn_c, a0 = c.  That is the fmaxf chain's value (a zero t0 is +0 here
+ *    whatever the sign of a zero tn_c), with ties going to x, then y, then z.  a0 = none exactly
+ *    when t0 == 0, and then every clipping axis has tn_c <= 0 <= tf_c and every other axis holds
+ *    0 <= ol_c <= nf: the origin lies in the closed grid, on its surface included.
+ *    t1 > t0 makes t0 finite.
+ *  Walk (A.3's, as the K2 input rule writes it), with sign / td from d:  s_c = sign(d_c),
+ *    td_c = 1.0f / fabsf(d_c) (+inf where d_c == 0); an axis whose td_c is not finite does not
+ *    move: s_c = 0, tm_c = +inf.  (td_c is finite exactly when the axis clips.)
+ *      p_c = ol_c + d_c * t0                         (multiply, add)
+ *      v_c = (int)fminf(fmaxf(floorf(p_c), 0.0f), nf - 1.0f)      (clamped before the conversion)
+ *      tm_c = ((float)(v_c + 1) - p_c) * td_c  for s_c > 0,  (p_c - (float)v_c) * td_c  for s_c < 0
+ *      face = 6 when a0 = none, else 2 a0 + (s_a0 > 0 ? 0 : 1);   te = t0;   steps = 0
+ *    Repeat at most VCT_VOXVIEW_STEPS_PER_CELL * n_l times:
+ *      1. steps += 1.  If cell v is solid: a hit, record (v_x + n_l (v_y + n_l v_z), face, steps,
+ *         bits of te * 2^l); end.
+ *      2. a = x if tm_x <= tm_y and tm_x <= tm_z, else y if tm_y <= tm_z, else z;
+ *         tn = t0 + tm_a  (tm_a before the addition of step 4).  If tn >= ll: a miss; end.
+ *      3. v_a += s_a.  If v_a < 0 or v_a >= n_l: a miss; end.
+ *      4. tm_a = tm_a + td_a;  face = 2 a + (s_a > 0 ? 0 : 1);  te = tn.
+ *    A miss is (0xFFFFFFFF, 7, steps, bits of +inf).  The cell is tested first, then stepped.
+ *    No t is a NaN: t0 is finite; ol_c and d_c * t0 are finite (|d_c| <= 1 up to rounding), so
+ *    p_c is finite or, by overflow of the sum, one infinity, never a NaN; v_c is an integer in
+ *    [0, n_l - 1]; td_c of a moving axis is finite and >= 2^-1 (not 0), so tm_c is a product of a
+ *    finite or infinite factor and a finite positive one; tm only grows by additions of a positive
+ *    finite td; tn = t0 + tm_a is finite plus (finite or one infinity).  d has a component of
+ *    magnitude >= 0.57 whose axis clips, and the a0 axis (or, for t0 = 0, every axis) has a p
+ *    inside the grid up to rounding, so the smallest tm is finite and the stepped axis moves.
+ *    The walk ends within 3 n_l steps: every step moves one axis by s_a = +-1, never back, and an
+ *    axis leaves [0, n_l) at its n_l-th step at the latest, so at most 3 (n_l - 1) + 1 cells are
+ *    tested.  The cap bounds the loop in the kernel and in the reference alike and is never
+ *    reached by legal arithmetic.
+ *  Solid.  Occupancy (level 0 only): K1's occupancy bit of the cell.  Alpha: T.a > 0 for the
+ *    level-l texel T of the cell, of any of the six faces on an anisotropic level >= 1 (a NaN
+ *    alpha is not > 0).
+ *  Colour of the hit cell c (the view):
+ *    RADIANCE  C = T.rgb at level 0 or in an isotropic pyramid; on an anisotropic level >= 1, with
+ *              f_c from d_c >= 0.0f and wd_c = d_c * d_c (A.5's faces and weights of direction d),
+ *              per channel  C = fmaf(wd_z, T_fz, fmaf(wd_y, T_fy, wd_x * T_fx)),  exactly as "cone
+ *              queries" combines a corner texel
+ *    ALPHA     the alpha of the same combination in all three channels
+ *    ALBEDO    albedo_occ.rgb of the voxel
+ *    NORMAL    fmaf(0.5f, n_c, 0.5f) of the voxel's normal
+ *    shade == 1:  C_c = C_c * k with k = VCT_VOXVIEW_SHADE_X, _Y or _Z for face >> 1 = 0, 1, 2 and
+ *    1.0f for face 6;  shade == 0 multiplies nothing.
+ *    linear4 = (C, 1.0f) on a hit, (+0, +0, +0, +0) on a miss.  rgba8 on a hit, alpha 255:
+ *    RADIANCE q(tone(C_c)), the composites' present step ("volumetric fog", Apply); the other
+ *    modes q(C_c) without the tone curve (they are not radiance).  rgba8 = 0 on a miss.
+ *  Skipping loads.  A form that tests fewer cells' texels must keep every step's arithmetic
+ *    (K2's discipline with its coarse bits).  In alpha mode K4's empty-space maps (b0, occ and the
+ *    zmaps of vct_internal.h) may be used while they describe the pyramid: they are built from the bit pattern of whole texels
+ *    (a texel that is not +0 in all four channels sets its bit), so a clear bit proves every face
+ *    of every texel below it +0, hence alpha = +0, not > 0, not solid.  The library's kernels
+ *    take the plain walk.
+ *  The section's literals (VCT_VOXVIEW_SHADE_X / _Y / _Z, VCT_VOXVIEW_STEPS_PER_CELL) stand with
+ *    the present step's, above. */
 
 #endif /* VCT_SPEC_H */

@@ -897,6 +897,10 @@ static const char* bad_gbuffer_input(const vct_camera* cam, uint32_t w, uint32_t
     if (!(s * m * m <= VCT_GBUF_FOCAL_LIMIT)) return "gbuffer: focal length above VCT_GBUF_FOCAL_LIMIT";
     return nullptr;
 }
+}  // extern "C"
+/* the same check for the other units (the voxel view's camera, vct_voxview.hip) */
+const char* vct::gbuffer_input_error(const vct_camera* cam, uint32_t w, uint32_t h) { return bad_gbuffer_input(cam, w, h); }
+extern "C" {
 
 vct_status vct_gbuffer_raycast_device(vct_ctx* c, const vct_camera* cam, uint32_t w, uint32_t h,
                                       float rough, float* pos4, float* nrm4, float* alb4) {

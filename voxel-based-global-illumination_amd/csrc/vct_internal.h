@@ -530,6 +530,10 @@ hipError_t launch_gbuffer_binned(vct_ctx* c, const vct_camera* cam, uint32_t w, 
 hipError_t launch_raycast(vct_ctx* c, const vct_camera* cam, uint32_t w, uint32_t h, float rough,
                           float4* pos, float4* nrm, float4* alb);
 
+// the "G-buffer input rule" of vct_spec.h on a camera and a frame size (vct_capi.cpp's
+// bad_gbuffer_input): nullptr, or what is wrong; cam must not be NULL
+const char* gbuffer_input_error(const vct_camera* cam, uint32_t w, uint32_t h);
+
 uint32_t tiles_for_rank(uint32_t w, uint32_t h, uint32_t rank, uint32_t world);
 // dst[j] += sum over i < n of src[2 i + j], j = 0, 1 (a NULL dst is skipped): the
 // multi-device trace folds the other devices' step / texel counters into the caller's

@@ -7,6 +7,7 @@
 //                [--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32]
 //                [--light SPEC]... [--shadow-tan T] [--sky Z[:H[:G]]] [--sky-view] [--mixed 2|4]
 //                [--fog DENSITY] [--temporal N] [--probes D] [--dynamic FILE.obj [--dynamic-offset x,y,z]]
+//                [--voxels LEVEL[:MODE]]...
 //   (devices > 1: one process drives that many GPUs through vct_create_multi)
 //   --model: the model matrix of the reference's draw, T(0,-1.75,0) S(0.2)
 //            (r_voxelization.cpp:26-29; default), or none;
@@ -36,6 +37,10 @@
 //   --probes: D in 1 .. 256: a D^3 grid of ambient-cube probes (include/vct_query.h) over the grid's
 //            AABB, built after every relight; the composite reads the probe-sampled plane in place of
 //            K4's diffuse plane (the specular cone is still traced); absent: K4's diffuse plane;
+//   --voxels: LEVEL[:MODE], repeatable: after the last frame, the voxel view (include/vct_voxview.h) of
+//            the frame's camera through pyramid level LEVEL is written next to the frame as
+//            <out stem>.voxels<LEVEL>-<MODE>.png, shaded by entry face.  MODE: radiance (default),
+//            alpha, albedo or normal; albedo and normal exist at level 0 only;
 //   --dynamic: a second model, voxelized as the context's dynamic layer (include/vct_dynamic.h)
 //            on top of the first one's grid; Kd materials only (its diffuse maps are not loaded).
 //            --dynamic-offset: a world-space translation applied after the model matrix of
@@ -136,6 +141,28 @@ static bool parse_sky(const std::string& spec, vct_sky* out) {
     return true;
 }
 
+// one --voxels LEVEL[:MODE] (see above); false: malformed
+struct VoxelView {
+    uint32_t level, mode;
+    std::string mode_name;
+};
+static bool parse_voxels(const std::string& spec, VoxelView* out) {
+    static const char* const names[4] = {"radiance", "alpha", "albedo", "normal"};   // VCT_VOXVIEW_* order
+    const size_t colon = spec.find(':');
+    const std::string lv = spec.substr(0, colon);
+    out->mode_name = colon == std::string::npos ? "radiance" : spec.substr(colon + 1);
+    char* end = nullptr;
+    const long l = std::strtol(lv.c_str(), &end, 10);
+    if (lv.empty() || lv[0] < '0' || lv[0] > '9' || *end || l > 10) return false;
+    out->level = (uint32_t)l;
+    for (uint32_t m = 0; m < 4; ++m)
+        if (out->mode_name == names[m]) {
+            out->mode = m;
+            return m < VCT_VOXVIEW_ALBEDO || l == 0;
+        }
+    return false;
+}
+
 // one --dynamic-offset x,y,z -> out[3]; false: malformed (not exactly three finite numbers)
 static bool parse_offset(const std::string& spec, float out[3]) {
     const char* p = spec.c_str();
@@ -164,6 +191,7 @@ int main(int argc, char** argv) {
     float fog_density = 0.0f;
     uint32_t temporal = 0;
     uint32_t probes = 0;
+    std::vector<VoxelView> voxels;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--model=reference") ref_model = true;
@@ -221,6 +249,15 @@ int main(int argc, char** argv) {
             }
             probes = (uint32_t)d;
         }
+        else if (a == "--voxels" || a.rfind("--voxels=", 0) == 0) {
+            const std::string v = a == "--voxels" ? (i + 1 < argc ? argv[++i] : "") : a.substr(9);
+            VoxelView vv;
+            if (!parse_voxels(v, &vv)) {
+                std::fprintf(stderr, "malformed --voxels %s (LEVEL[:radiance|alpha|albedo|normal]; albedo and normal at level 0)\n", v.c_str());
+                return 2;
+            }
+            voxels.push_back(vv);
+        }
         else if (a == "--dynamic-offset" || a.rfind("--dynamic-offset=", 0) == 0) {
             const std::string spec = a == "--dynamic-offset" ? (i + 1 < argc ? argv[++i] : "") : a.substr(17);
             if (!parse_offset(spec, dyn_offset)) { std::fprintf(stderr, "malformed --dynamic-offset %s\n", spec.c_str()); return 2; }
@@ -237,7 +274,7 @@ int main(int argc, char** argv) {
     if (sky_view && !has_sky) { std::fprintf(stderr, "--sky-view needs --sky Z[:H[:G]]\n"); return 2; }
     if (pos.empty()) {
         std::fprintf(stderr, "usage: %s model.obj [grid] [width] [height] [frames] [out.ppm] [devices] "
-                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] [--sky Z[:H[:G]]] [--sky-view] [--mixed 2|4] [--fog DENSITY] [--temporal N] [--probes D] "
+                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] [--sky Z[:H[:G]]] [--sky-view] [--mixed 2|4] [--fog DENSITY] [--temporal N] [--probes D] [--voxels LEVEL[:MODE]]... "
                              "[--dynamic FILE.obj [--dynamic-offset x,y,z]] "
                              "[--light dir:d:rgb | point:p:rgb:range | spot:p:d:rgb:range:inner:outer]...\n",
                      argv[0]);
@@ -311,5 +348,15 @@ int main(int argc, char** argv) {
     if (!r->WritePPM(out)) return 1;
     if (!linear.empty() && !r->WriteLinear(linear)) return 1;
     std::printf("wrote %s\n", out.c_str());
+    for (const VoxelView& v : voxels) {
+        const size_t dot = out.rfind('.'), slash = out.rfind('/');
+        const std::string stem = dot != std::string::npos && (slash == std::string::npos || dot > slash) ? out.substr(0, dot) : out;
+        const std::string png = stem + ".voxels" + std::to_string(v.level) + "-" + v.mode_name + ".png";
+        if (!r->WriteVoxelView(png, v.level, v.mode)) {
+            std::fprintf(stderr, "voxel view %u:%s failed: %s\n", v.level, v.mode_name.c_str(), r->error().c_str());
+            return 1;
+        }
+        std::printf("wrote %s\n", png.c_str());
+    }
     return 0;
 }

@@ -233,6 +233,51 @@ bool LoadPng(const std::string& path, PngImage* out, std::string* err) {
     return DecodePng(buf.data(), buf.size(), out, err);
 }
 
+// one chunk: length, type, data, CRC of type + data
+static void put_chunk(std::vector<uint8_t>* f, const char type[4], const uint8_t* data, size_t n) {
+    const auto be = [&](uint32_t v) { for (int s = 24; s >= 0; s -= 8) f->push_back((uint8_t)(v >> s)); };
+    be((uint32_t)n);
+    const size_t at = f->size();
+    f->insert(f->end(), type, type + 4);
+    if (n) f->insert(f->end(), data, data + n);
+    be((uint32_t)crc32(0L, f->data() + at, (uInt)(n + 4)));
+}
+
+bool EncodePng(const PngImage& img, std::vector<uint8_t>* file, std::string* err) {
+    static const uint8_t sig[8] = {137, 80, 78, 71, 13, 10, 26, 10};
+    static const uint8_t colour_type[5] = {0, 0, 4, 2, 6};          // by channel count
+    if (img.comp < 1 || img.comp > 4 || img.width == 0 || img.height == 0) return fail(err, "png: nothing to encode");
+    const size_t row = (size_t)img.width * img.comp;
+    if (img.data.size() != row * img.height) return fail(err, "png: data does not match width x height x comp");
+    std::vector<uint8_t> raw((row + 1) * img.height);               // filter byte 0 (None) before every row
+    for (uint32_t y = 0; y < img.height; ++y) {
+        raw[(row + 1) * y] = 0;
+        std::memcpy(&raw[(row + 1) * y + 1], &img.data[row * y], row);
+    }
+    uLongf zn = compressBound((uLong)raw.size());
+    std::vector<uint8_t> z(zn);
+    if (compress2(z.data(), &zn, raw.data(), (uLong)raw.size(), 6) != Z_OK) return fail(err, "png: deflate failed");
+    file->assign(sig, sig + 8);
+    uint8_t ihdr[13];
+    for (int k = 0; k < 4; ++k) {
+        ihdr[k] = (uint8_t)(img.width >> (24 - 8 * k));
+        ihdr[4 + k] = (uint8_t)(img.height >> (24 - 8 * k));
+    }
+    ihdr[8] = 8; ihdr[9] = colour_type[img.comp]; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;
+    put_chunk(file, "IHDR", ihdr, sizeof ihdr);
+    put_chunk(file, "IDAT", z.data(), zn);
+    put_chunk(file, "IEND", nullptr, 0);
+    return true;
+}
+
+bool WritePng(const std::string& path, const PngImage& img, std::string* err) {
+    std::vector<uint8_t> file;
+    if (!EncodePng(img, &file, err)) return false;
+    std::ofstream f(path, std::ios::binary);
+    if (!f || !f.write((const char*)file.data(), (std::streamsize)file.size())) return fail(err, "cannot write " + path);
+    return true;
+}
+
 bool ExpandToRgba(const PngImage& img, std::vector<uint8_t>* rgba, std::string* err) {
     if (img.comp == 2) return fail(err, "2-channel texture: the reference's GL format is undefined (model.cpp:200-206)");
     if (img.comp != 1 && img.comp != 3 && img.comp != 4) return fail(err, "unsupported channel count");

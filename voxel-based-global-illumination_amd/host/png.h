@@ -1,4 +1,4 @@
-// png.h — PNG decoding for the diffuse maps of the scene loader.
+// png.h — PNG decoding for the diffuse maps of the scene loader (and a plain encoder).
 //
 // The reference decodes its material textures with stb_image
 // (`stbi_load(filename, &w, &h, &nrComponents, 0)`, scene/model.cpp:197) and
@@ -26,6 +26,11 @@ struct PngImage {
 
 bool DecodePng(const uint8_t* file, size_t bytes, PngImage* out, std::string* err);
 bool LoadPng(const std::string& path, PngImage* out, std::string* err);
+
+// The way back, for the frames the host writes (the voxel view): 8 bits per channel, 1..4
+// channels, no interlace, filter None, one IDAT; DecodePng reads it back unchanged.
+bool EncodePng(const PngImage& img, std::vector<uint8_t>* file, std::string* err);
+bool WritePng(const std::string& path, const PngImage& img, std::string* err);
 
 // RGBA8 texels as the reference's GL upload samples them: 1 channel (GL_RED) ->
 // (r, 0, 0, 255), 3 (GL_RGB) -> (r, g, b, 255), 4 -> as stored.  2 channels: the

@@ -9,6 +9,7 @@
 #include <cstring>
 
 #include "assets.h"
+#include "png.h"
 
 namespace vcthost {
 
@@ -347,6 +348,34 @@ bool ConeTraceRenderer::WritePPM(const std::string& path) {
         std::fwrite(row.data(), 1, row.size(), f);
     }
     std::fclose(f);
+    return true;
+}
+
+bool ConeTraceRenderer::WriteVoxelView(const std::string& path, uint32_t level, uint32_t mode) {
+    if (!ctx_) return false;
+    const size_t px = (size_t)s_.width * s_.height;
+    void* rgba = nullptr;
+    if (!check(vct_device_alloc(ctx_, px * 4, &rgba), "alloc voxel view")) return false;
+    std::vector<uint32_t> img(px);
+    vct_voxel_view_args a{};
+    a.width = s_.width; a.height = s_.height;
+    a.level = level; a.mode = mode; a.shade = 1;
+    a.rgba8 = (uint32_t*)rgba;
+    const bool ok = check(vct_voxel_view_device(ctx_, &cam_, &a), "voxel view") &&
+                    check(vct_memcpy(ctx_, img.data(), rgba, px * 4, 1), "download voxel view");
+    vct_device_free(ctx_, rgba);
+    if (!ok) return false;
+    PngImage out;
+    out.width = s_.width; out.height = s_.height; out.comp = 3;
+    out.data.resize(px * 3);
+    for (size_t i = 0; i < px; ++i)
+        for (int k = 0; k < 3; ++k) out.data[3 * i + k] = (uint8_t)(img[i] >> (8 * k));
+    std::string err;
+    if (!WritePng(path, out, &err)) {
+        error_ = err;
+        std::fprintf(stderr, "voxel view: %s\n", err.c_str());
+        return false;
+    }
     return true;
 }
 

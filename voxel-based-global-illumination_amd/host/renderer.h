@@ -100,6 +100,9 @@ public:
     bool WritePPM(const std::string& path);
     // the same composite before tone mapping: width x height x 4 float32, row 0 = top, raw little-endian
     bool WriteLinear(const std::string& path);
+    // the voxel view (include/vct_voxview.h) of the last Render()'s camera at `level` in `mode`
+    // (VCT_VOXVIEW_*), shaded by entry face, at the frame's size -> PNG (RGB)
+    bool WriteVoxelView(const std::string& path, uint32_t level, uint32_t mode);
 
 private:
     bool check(vct_status s, const char* what);

@@ -127,6 +127,32 @@ int vcth_decode_png(const uint8_t* file, size_t bytes, uint8_t** data, uint32_t*
     return 0;
 }
 
+int vcth_encode_png(const uint8_t* data, uint32_t width, uint32_t height, int comp, uint8_t** file, size_t* file_bytes,
+                    char* err, int errlen) {
+    if (!data || !file || !file_bytes || comp < 1 || comp > 4) return -1;
+    *file = nullptr;
+    std::string e;
+    std::vector<uint8_t> out;
+    try {
+        vcthost::PngImage img;
+        img.width = width; img.height = height; img.comp = comp;
+        img.data.assign(data, data + (size_t)width * height * comp);
+        if (!vcthost::EncodePng(img, &out, &e)) {
+            put_err(err, errlen, e);
+            return -1;
+        }
+    } catch (const std::exception& ex) {
+        put_err(err, errlen, std::string("vcth_encode_png: ") + ex.what());
+        return -1;
+    }
+    uint8_t* p = (uint8_t*)std::malloc(out.size());
+    if (!p) return -1;
+    std::memcpy(p, out.data(), out.size());
+    *file = p;
+    *file_bytes = out.size();
+    return 0;
+}
+
 void vcth_free_image(uint8_t* data) { std::free(data); }
 
 void vcth_free(vcth_model* m) { delete m; }

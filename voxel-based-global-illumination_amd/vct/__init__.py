@@ -33,6 +33,7 @@ from ._lib import VCT_CONES_DIFFUSE, VCT_CONES_SPECULAR, VctMixedHoles, VctMixed
 from ._lib import VctFog
 from ._lib import VctTemporalArgs, VctTemporalParams
 from ._lib import VctCone, VctConeQueryArgs, VctProbeGrid
+from ._lib import VctVoxelPickArgs, VctVoxelViewArgs
 
 __all__ = ["VctTemporalParams","Context", "VctError", "VctConfig", "VctCamera", "tiles_for_rank", "tile_offset", "VERTEX_FLOATS",
            "VCT_ALL_RANKS", "comm_frame_layout", "VctLight", "directional_light", "point_light", "spot_light",
@@ -696,6 +697,41 @@ class Context:
                        self._dev(state, "state", _I32, n), self._dev(pos4, "pos4", _F32, 4 * count),
                        self._dev(nrm4, "nrm4", _F32, 4 * count), int(count), self._dev(out4, "out4", _F32, 4 * count),
                        self._dev(misses, "misses", _I32, 1)), "probe_sample")
+
+    # -- the voxel view and ray picking (include/vct_voxview.h) ---------------
+    def voxel_pick_device(self, org4, dir4, count, hit4, level=0, solid=_lib.VCT_VOXPICK_OCCUPANCY, cells=None):
+        """vct_voxel_pick_device: walks `count` rays -- org4 (world origin) and dir4 (direction,
+        .w = t_lim in level-0 voxel units), float32 device tensors [count, 4] -- through `level`
+        and writes (cell, face, steps, float bits of t) per ray into hit4, an int32 device tensor
+        [count, 4].  solid: VCT_VOXPICK_OCCUPANCY (level 0) or VCT_VOXPICK_ALPHA.  cells: a
+        1-element int64 device tensor that the call adds the cells it tested to."""
+        fn = _lib.bind_voxview_extension(self.lib, "vct_voxel_pick_device")
+        a = VctVoxelPickArgs()
+        a.org4 = self._dev(org4, "org4", _F32, 4 * count)
+        a.dir4 = self._dev(dir4, "dir4", _F32, 4 * count)
+        a.count, a.level, a.solid = int(count), int(level), int(solid)
+        a.hit4 = self._dev(hit4, "hit4", _I32, 4 * count)
+        a.cells = self._dev(cells, "cells", _I64, 1)
+        self._check(fn(self.h, C.byref(a)), "voxel_pick")
+
+    def voxel_view_device(self, cam, width, height, level=0, mode=_lib.VCT_VOXVIEW_RADIANCE, shade=False,
+                          linear4=None, rgba8=None, hit4=None, cells=None):
+        """vct_voxel_view_device: the voxel view of `cam` at `level` in `mode` (VCT_VOXVIEW_*) into
+        any of linear4 (float32 [h, w, 4]), rgba8 (int32 [h, w]) and hit4 (int32 [h, w, 4], the
+        records of voxel_pick_device); cells as there."""
+        fn = _lib.bind_voxview_extension(self.lib, "vct_voxel_view_device")
+        if hasattr(cam, "to_ctypes"):
+            cam = cam.to_ctypes()
+        if not isinstance(cam, VctCamera):
+            raise VctError(_EINVAL, f"voxel_view: expected a camera, got {type(cam).__name__}")
+        a = VctVoxelViewArgs()
+        a.width, a.height, a.level, a.mode, a.shade = int(width), int(height), int(level), int(mode), int(bool(shade))
+        n = width * height
+        a.linear4 = self._dev(linear4, "linear4", _F32, 4 * n)
+        a.rgba8 = self._dev(rgba8, "rgba8", _I32, n)
+        a.hit4 = self._dev(hit4, "hit4", _I32, 4 * n)
+        a.cells = self._dev(cells, "cells", _I64, 1)
+        self._check(fn(self.h, C.byref(cam), C.byref(a)), "voxel_view")
 
     # -- volumetric fog (include/vct_fog.h) ----------------------------------
     def _fog(self, fog, what):

@@ -78,6 +78,15 @@ SKY_VIEW_EXTENSIONS = ("vct_sky_specular_device", "vct_sky_background_device")
 QUERY_EXTENSIONS = ("vct_cone_query_device", "vct_probe_build_device", "vct_probe_sample_device")
 VCT_QUERY_MAX_STEPS, VCT_PROBE_MAX_DIM = 4096, 256
 
+# include/vct_voxview.h: the voxel view and ray picking, likewise HIP only (bind_voxview_extension)
+VOXVIEW_EXTENSIONS = ("vct_voxel_pick_device", "vct_voxel_view_device")
+VCT_VOXPICK_OCCUPANCY, VCT_VOXPICK_ALPHA = 0, 1
+VCT_VOXVIEW_RADIANCE, VCT_VOXVIEW_ALPHA, VCT_VOXVIEW_ALBEDO, VCT_VOXVIEW_NORMAL = 0, 1, 2, 3
+VCT_VOXVIEW_MODES = {"radiance": 0, "alpha": 1, "albedo": 2, "normal": 3}
+VCT_VOXHIT_FACE_INSIDE, VCT_VOXHIT_FACE_MISS, VCT_VOXHIT_CELL_MISS = 6, 7, 0xFFFFFFFF
+VCT_VOXVIEW_SHADE = (0.8, 1.0, 0.6)          # VCT_VOXVIEW_SHADE_X / _Y / _Z (include/vct_spec.h)
+VCT_VOXVIEW_STEPS_PER_CELL = 3
+
 STATUS = {0: "VCT_OK", 1: "VCT_EINVAL", 2: "VCT_ENOMEM", 3: "VCT_EDEVICE", 4: "VCT_ECOMM", 5: "VCT_ESTATE"}
 
 
@@ -247,6 +256,32 @@ class VctProbeGrid(C.Structure):         # vct_probe_grid, 28 bytes
         ("origin", C.c_float * 3),
         ("spacing", C.c_float),
         ("dims", C.c_uint32 * 3),
+    ]
+
+
+class VctVoxelPickArgs(C.Structure):    # vct_voxel_pick_args
+    _fields_ = [
+        ("org4", C.c_void_p),
+        ("dir4", C.c_void_p),
+        ("count", C.c_uint32),
+        ("level", C.c_uint32),
+        ("solid", C.c_uint32),
+        ("hit4", C.c_void_p),
+        ("cells", C.c_void_p),
+    ]
+
+
+class VctVoxelViewArgs(C.Structure):    # vct_voxel_view_args
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("level", C.c_uint32),
+        ("mode", C.c_uint32),
+        ("shade", C.c_uint32),
+        ("linear4", C.c_void_p),
+        ("rgba8", C.c_void_p),
+        ("hit4", C.c_void_p),
+        ("cells", C.c_void_p),
     ]
 
 
@@ -537,6 +572,25 @@ def bind_query_extension(lib: C.CDLL, name: str):
     except AttributeError:
         raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
                              "(include/vct_query.h is implemented by the HIP library only)") from None
+    fn.restype = res
+    fn.argtypes = args
+    return fn
+
+
+def bind_voxview_extension(lib: C.CDLL, name: str):
+    """The include/vct_voxview.h function `name` of `lib`, with its signature declared;
+    AttributeError (naming the library) if this implementation does not export it."""
+    P, i32 = C.c_void_p, C.c_int32
+    sig = {
+        "vct_voxel_pick_device": (i32, [P, C.POINTER(VctVoxelPickArgs)]),
+        "vct_voxel_view_device": (i32, [P, C.POINTER(VctCamera), C.POINTER(VctVoxelViewArgs)]),
+    }
+    res, args = sig[name]
+    try:
+        fn = getattr(lib, name)
+    except AttributeError:
+        raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
+                             "(include/vct_voxview.h is implemented by the HIP library only)") from None
     fn.restype = res
     fn.argtypes = args
     return fn
