@@ -140,6 +140,9 @@
  *    contribution is below 2^15 * 2^105 * 2 = 2^121 and the sum below 2^127 < FLT_MAX:
  *    VCT_COLOR_LIMIT = 2^127 / (VCT_KD_LIMIT * 2 * VCT_MAX_LIGHTS) = 2^105. */
 #define VCT_COLOR_LIMIT     4.05648192e31f   /* 2^105 exactly */
+/* "environment sky" (below): the largest texel of a map and the largest scale of a record, so
+ * that Env <= 2^104 (1 + 2^-21) stays below VCT_COLOR_LIMIT */
+#define VCT_ENV_TEXEL_LIMIT 4503599627370496.0f  /* 2^52 exactly */
 
 /* G-buffer input rule (what a camera, a frame size and a mesh mean to vct_gbuffer_raycast_device
  * and vct_gbuffer_raster_device; one rule for both calls; every implementation restates it):
@@ -823,5 +826,66 @@
  *    take the plain walk.
  *  The section's literals (VCT_VOXVIEW_SHADE_X / _Y / _Z, VCT_VOXVIEW_STEPS_PER_CELL) stand with
  *    the present step's, above. */
+
+/* ---- environment sky (vct_set_env / vct_env_*_device / vct_inject_env, include/vct_env.h;
+ *      tests/env_ref.py restates it) ------------------------------------------------------------
+ *  All arithmetic is float32, one rounding per operation, no contraction; the fused operations
+ *    are the fmaf() calls named here.  dot3 is "local lights"'.
+ *  The map: S x S RGBA texels, S = 2^lgS, 1 <= S <= VCT_ENV_MAX_DIM (2048), octahedral, row 0 =
+ *    p.y = -1; texel (x, y) of level j is M_j[y][x].  Input rule of a texel: r, g, b finite, sign
+ *    bit clear (-0.0f is refused), <= VCT_ENV_TEXEL_LIMIT = 2^52; alpha is carried through the
+ *    mip rule and never read.  Level j has S_j = S >> j texels per side, j = 0 .. lgS, and per
+ *    channel
+ *      M_{j+1}[y][x] = ((M_j[2y][2x] + M_j[2y][2x+1]) + (M_j[2y+1][2x] + M_j[2y+1][2x+1])) * 0.25f
+ *    (three adds, one multiply).  A constant map is that constant at every level (2c, 4c and
+ *    c are exact below 2^54).
+ *  The record (frame, scale): every component of frame finite; with the dot products taken in
+ *    double, |frame[i].frame[i] - 1| <= VCT_GBUF_ORTHO_EPS and |frame[i].frame[j]| <=
+ *    VCT_GBUF_ORTHO_EPS (the camera's rule of the "G-buffer input rule"; handedness is not
+ *    tested); scale finite, sign bit clear, <= VCT_ENV_TEXEL_LIMIT.
+ *  Env(d, tau), for any direction d and any tau:
+ *    1. e_c = dot3(frame[c], d), c = x, y, z;  s = (|e.x| + |e.y|) + |e.z|.
+ *       Degenerate: unless s > 0 and s < +inf (a NaN, infinite or zero d, or an overflowing
+ *       sum), E = M_lgS[0][0], the map's mean, whatever tau is; go to step 5's last line.  This
+ *       is the counterpart of "sky light"'s horizon colour for a NaN u.
+ *    2. p = (e.x / s, e.y / s).  If e.z < 0.0f (-0.0f is not):
+ *         p = ((1.0f - |p.y|) * copysignf(1.0f, p.x), (1.0f - |p.x|) * copysignf(1.0f, p.y))
+ *       both components from the unfolded p.  |p_c| <= 1.
+ *    3. x = fminf(fmaxf(tau * (float)S, 1.0f), (float)S);  m = fminf(spec_log2(x), (float)lgS)
+ *       (A.6's spec_log2);  j0 = (int)m;  fr = m - (float)j0.  A NaN or negative tau gives x = 1,
+ *       m = 0; tau >= 1 gives m = lgS (spec_log2 of a power of two is exact).  m is what
+ *       vct_env_lookup_device returns in out4.w, for a degenerate d too.
+ *    4. B_j, the bilinear sample of level j, per channel:
+ *         u = (p.x * 0.5f + 0.5f) * (float)S_j - 0.5f;  v likewise from p.y
+ *         i0 = floorf(u), fu = u - i0;  k0 = floorf(v), fv = v - k0     (-1 <= i0, k0 <= S_j - 1)
+ *         a = T(i0, k0), b = T(i0 + 1, k0), c = T(i0, k0 + 1), d = T(i0 + 1, k0 + 1)
+ *         t0 = fmaf(fu, b - a, a);  t1 = fmaf(fu, d - c, c);  B_j = fmaf(fv, t1 - t0, t0)
+ *       T(x, y), a tap at integer (x, y): xc = min(max(x, 0), S_j - 1), yc likewise;
+ *         T(x, y) = M_j[x == xc ? yc : S_j - 1 - yc][y == yc ? xc : S_j - 1 - xc]
+ *       i.e. a tap whose x lies outside [0, S_j) takes x clamped and y mirrored, a tap whose y
+ *       lies outside takes y clamped and x mirrored, and a tap outside in both (a corner) takes
+ *       both mirrors.  That is the octahedral fold: the texel across an edge of the square is
+ *       the one mirrored along that edge, so no level has a seam.
+ *    5. E = B_j0;  if fr > 0 and j0 < lgS:  E = fmaf(fr, B_{j0+1} - B_j0, B_j0)  (per channel).
+ *       Env_c = E_c * scale.
+ *    A constant map c returns c * scale in every bit at every d and tau: b - a = +0, so every
+ *    fmaf returns its addend.
+ *  Bound: a fmaf(f, y - x, x) with 0 <= f < 1 lies within one rounding of [x, y], so
+ *    E <= 2^52 (1 + 2^-21) and Env <= 2^104 (1 + 2^-21) < VCT_COLOR_LIMIT = 2^105: the bound
+ *    argument of "sky light" (A * Sk below 2^15 * 2^105 * ~3 < 2^122; level 0 stays finite)
+ *    carries over unchanged.
+ *  vct_env_cones_device / vct_inject_env: "sky light" with its receiver, cones, a_k and T_k
+ *    unchanged, and
+ *      acc_c = fmaf(w_k * T_k, Env_c(d_k, tau_set), acc_c);   vis = fmaf(w_k, T_k, vis)
+ *    tau_set = VCT_TAN30 for 1 and 9 cones, VCT_TAN20 for 16 (the set's aperture: one level pair
+ *    per context).  A non-finite d_k takes the degenerate branch.  The diffuse add and the
+ *    per-voxel L_c = L_c + A_c * Sk_c are "sky light"'s.
+ *  vct_env_specular_device: "sky in view"'s specular cone unchanged, S_c = T * Env_c(r, tau)
+ *    with the pixel's clamped tau (the aperture and the level pair are per lane).
+ *  vct_env_background_device: "sky in view"'s background with c = Env(d, 0.0f) (level 0).
+ *  With a constant map c, scale = 1 and any legal frame each of the four equals its vct_sky
+ *    counterpart with zenith = horizon = ground = c in every bit (Sky_c = (c + 0 * s_up) + 0 *
+ *    s_dn = c for finite s).
+ *  The section's literal (VCT_ENV_TEXEL_LIMIT) stands with VCT_COLOR_LIMIT, above. */
 
 #endif /* VCT_SPEC_H */

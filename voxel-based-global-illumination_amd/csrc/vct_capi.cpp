@@ -333,6 +333,7 @@ void vct_destroy(vct_ctx* c) {
     emission_free(c);
     dynamic_free(c);
     fog_free(c);
+    env_free(c);
     for (auto& s : c->scratch)
         if (s.p) (void)hipFree(s.p);
     for (auto& ss : c->k4s)

@@ -200,6 +200,18 @@ struct Fog {
     unsigned long long* dbg_ambient_steps = nullptr;   // add their light-cone / ambient K4 steps to
 };
 
+// The environment-map sky (vct_env.hip; vct_spec.h "environment sky").  The map of the last
+// vct_set_env with its mip chain, one allocation: level j is (size >> j)^2 float4 texels, row
+// major, row 0 = p.y = -1, starting at texel 4 (size^2 - (size >> j)^2) / 3 (the levels back to
+// back).  Replaced as a whole, after the ctx stream has drained.
+struct Env {
+    float4* map = nullptr;
+    uint32_t size = 0, lg = 0;       // size 0: no map
+    int path = 0;                    // address path of the last env march: 32 or 64 (vct_debug_env_path)
+    bool profile = false;            // vct_debug_env_mips: time the mip build of vct_set_env with events
+    float mip_ms = 0.0f;             // the mip kernels of the last timed vct_set_env
+};
+
 // K4's per-launch scratch, one set per stream: K4 launches on different streams may run
 // concurrently (a host that overlaps consecutive frames), so the cone-split hand-over
 // and the ray-reorder buffers belong to the stream, not to the context.
@@ -332,6 +344,7 @@ struct vct_ctx {
     vct::Emission em;                   // emission grid of vct_voxelize_emission*
     vct::Dynamic dyn;                   // dynamic layer of vct_voxelize_dynamic*
     vct::Fog fog;                       // scatter volume of vct_build_fog
+    vct::Env env;                       // map and mips of vct_set_env
     uint32_t grid_epoch = 0;            // bumped by every voxelization (a new scene for the tuner)
     vct::StepRow* step_tab = nullptr;   // [kMaxStepRows] diffuse-cone step table (device)
     unsigned* spec_keys = nullptr;      // [2 * kSpecSlots]: specular table keys (~0u free), then states
@@ -499,6 +512,8 @@ inline bool fog_current(const vct_ctx* c) {
            c->fog.serial == c->grid.mips_serial;
 }
 void fog_free(vct_ctx* c);
+// environment-map sky (vct_env.hip): release with the context
+void env_free(vct_ctx* c);
 // ray reordering (variant 0x8000, vct_reorder.hip): *perm = the frame's pixels sorted by the
 // Morton code of their cone origin's voxel, background last (device, w * h entries)
 // (perm_spec, nullable: a second order for the specular part, by cell and cone aperture)

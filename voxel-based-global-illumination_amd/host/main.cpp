@@ -5,7 +5,7 @@
 //
 //   vct_headless <model.obj> [grid=256] [width=800] [height=600] [frames=5] [out.ppm] [devices=1]
 //                [--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32]
-//                [--light SPEC]... [--shadow-tan T] [--sky Z[:H[:G]]] [--sky-view] [--mixed 2|4]
+//                [--light SPEC]... [--shadow-tan T] [--sky Z[:H[:G]]] [--env FILE[:SCALE]] [--sky-view] [--mixed 2|4]
 //                [--fog DENSITY] [--temporal N] [--probes D] [--dynamic FILE.obj [--dynamic-offset x,y,z]]
 //                [--voxels LEVEL[:MODE]]...
 //   (devices > 1: one process drives that many GPUs through vct_create_multi)
@@ -24,6 +24,11 @@
 //            after the mips and before the bounces, and added per pixel to the diffuse term;
 //   --sky-view: with --sky, the sky in view (include/vct_sky_view.h): the sky is also seen by the
 //            specular cone of every pixel, and the background shows it instead of the clear colour;
+//   --env:    FILE[:SCALE]: an environment map (include/vct_env.h) in the sky's place: FILE is raw
+//            little-endian float32 RGBA texels of an octahedral square, S from the file size (S * S
+//            * 16 bytes, S a power of two <= 2048; any other size is a usage error), the map's +z at
+//            the world's +y, SCALE (default 1) its intensity.  It replaces --sky in the per-voxel
+//            inject and the diffuse call and, with --sky-view, in the specular and background calls;
 //   --mixed:  2 or 4: the frame is traced at mixed resolution (include/vct_mixed.h): diffuse cones on
 //            a frame that many times smaller per axis, upsampled, holes traced exactly, the
 //            specular cone at full resolution; absent: the full-resolution trace;
@@ -141,6 +146,46 @@ static bool parse_sky(const std::string& spec, vct_sky* out) {
     return true;
 }
 
+// one --env FILE[:SCALE] (see above) -> the texels, their size and the scale; false, with *why:
+// a file that cannot be read or whose size is not S * S * 16 bytes for a power of two S in
+// 1 .. VCT_ENV_MAX_DIM, or a SCALE that is not a finite number >= 0.  A suffix after the last ':'
+// that is not a number belongs to the file name.
+static bool parse_env(const std::string& spec, std::vector<float>* texels, uint32_t* size, float* scale,
+                      std::string* why) {
+    std::string file = spec;
+    *scale = 1.0f;
+    const size_t colon = spec.rfind(':');
+    if (colon != std::string::npos && colon + 1 < spec.size()) {
+        const std::string tail = spec.substr(colon + 1);
+        char* end = nullptr;
+        const float v = std::strtof(tail.c_str(), &end);
+        if (end != tail.c_str() && *end == '\0') {
+            if (!std::isfinite(v) || std::signbit(v)) { *why = "SCALE must be finite and >= 0"; return false; }
+            *scale = v;
+            file = spec.substr(0, colon);
+        }
+    }
+    std::FILE* f = std::fopen(file.c_str(), "rb");
+    if (!f) { *why = "cannot open " + file; return false; }
+    std::fseek(f, 0, SEEK_END);
+    const long bytes = std::ftell(f);
+    std::fseek(f, 0, SEEK_SET);
+    uint32_t s = 0;
+    for (uint32_t k = 1; k <= VCT_ENV_MAX_DIM; k <<= 1)
+        if (bytes == (long)k * (long)k * 16) s = k;
+    if (!s) {
+        std::fclose(f);
+        *why = file + ": " + std::to_string(bytes) + " bytes is not S*S*16 for a power of two S <= " + std::to_string(VCT_ENV_MAX_DIM);
+        return false;
+    }
+    texels->resize((size_t)s * s * 4);
+    const size_t got = std::fread(texels->data(), 16, (size_t)s * s, f);
+    std::fclose(f);
+    if (got != (size_t)s * s) { *why = "short read of " + file; return false; }
+    *size = s;
+    return true;
+}
+
 // one --voxels LEVEL[:MODE] (see above); false: malformed
 struct VoxelView {
     uint32_t level, mode;
@@ -187,6 +232,10 @@ int main(int argc, char** argv) {
     float shadow_tan = 0.0f;
     bool has_sky = false, sky_view = false;
     vct_sky sky{};
+    bool has_env = false;
+    std::vector<float> env_texels;
+    uint32_t env_size = 0;
+    float env_scale = 1.0f;
     uint32_t mixed = 0;
     float fog_density = 0.0f;
     uint32_t temporal = 0;
@@ -215,6 +264,15 @@ int main(int argc, char** argv) {
             has_sky = true;
         }
         else if (a == "--sky-view") sky_view = true;
+        else if (a == "--env" || a.rfind("--env=", 0) == 0) {
+            const std::string spec = a == "--env" ? (i + 1 < argc ? argv[++i] : "") : a.substr(6);
+            std::string why;
+            if (spec.empty() || !parse_env(spec, &env_texels, &env_size, &env_scale, &why)) {
+                std::fprintf(stderr, "malformed --env %s (%s)\n", spec.c_str(), spec.empty() ? "FILE[:SCALE]" : why.c_str());
+                return 2;
+            }
+            has_env = true;
+        }
         else if (a == "--mixed" || a.rfind("--mixed=", 0) == 0) {
             const std::string v = a == "--mixed" ? (i + 1 < argc ? argv[++i] : "") : a.substr(8);
             if (v != "2" && v != "4") { std::fprintf(stderr, "malformed --mixed %s (2 or 4)\n", v.c_str()); return 2; }
@@ -271,10 +329,10 @@ int main(int argc, char** argv) {
         else if (a.rfind("--", 0) == 0) { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
         else pos.push_back(a);
     }
-    if (sky_view && !has_sky) { std::fprintf(stderr, "--sky-view needs --sky Z[:H[:G]]\n"); return 2; }
+    if (sky_view && !has_sky && !has_env) { std::fprintf(stderr, "--sky-view needs --sky Z[:H[:G]] or --env FILE[:SCALE]\n"); return 2; }
     if (pos.empty()) {
         std::fprintf(stderr, "usage: %s model.obj [grid] [width] [height] [frames] [out.ppm] [devices] "
-                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] [--sky Z[:H[:G]]] [--sky-view] [--mixed 2|4] [--fog DENSITY] [--temporal N] [--probes D] [--voxels LEVEL[:MODE]]... "
+                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] [--sky Z[:H[:G]]] [--env FILE[:SCALE]] [--sky-view] [--mixed 2|4] [--fog DENSITY] [--temporal N] [--probes D] [--voxels LEVEL[:MODE]]... "
                              "[--dynamic FILE.obj [--dynamic-offset x,y,z]] "
                              "[--light dir:d:rgb | point:p:rgb:range | spot:p:d:rgb:range:inner:outer]...\n",
                      argv[0]);
@@ -297,6 +355,10 @@ int main(int argc, char** argv) {
     s.has_sky = has_sky;
     s.sky = sky;
     s.sky_view = sky_view;
+    s.has_env = has_env;
+    s.env_texels = std::move(env_texels);
+    s.env_size = env_size;
+    s.env.scale = env_scale;
     s.mixed_factor = mixed;
     s.fog_density = fog_density;
     s.temporal_len = temporal;

@@ -31,6 +31,7 @@ ConeTraceRenderer::ConeTraceRenderer(const std::string& model_name, const ConeTr
     for (auto& p : out_)
         if (!check(vct_device_alloc(ctx_, fb, &p), "alloc output")) return;
     if (!check(vct_device_alloc(ctx_, 8, &counter_), "alloc counter")) return;
+    if (s.has_env && !check(vct_set_env(ctx_, s.env_texels.data(), s.env_size), "vct_set_env")) return;
     if (s.temporal_len) {
         for (auto& p : hist_)
             if (!check(vct_device_alloc(ctx_, fb, &p), "alloc history plane")) return;
@@ -121,7 +122,11 @@ bool ConeTraceRenderer::relight() {
         return false;
     }
     if (!check(vct_build_mips(ctx_), "vct_build_mips")) return false;
-    if (s_.has_sky && !check(vct_inject_sky(ctx_, &s_.sky), "vct_inject_sky")) return false;
+    if (s_.has_env) {   // the map takes the sky's place (one of the two per level 0)
+        if (!check(vct_inject_env(ctx_, &s_.env), "vct_inject_env")) return false;
+    } else if (s_.has_sky && !check(vct_inject_sky(ctx_, &s_.sky), "vct_inject_sky")) {
+        return false;
+    }
     if (s_.bounces && !check(vct_inject_bounces(ctx_, s_.bounces), "vct_inject_bounces")) return false;
     if (s_.fog_density > 0.0f) {   // the scatter volume of the finished pyramid, one visibility cone per light
         const std::vector<vct_light> lights = frame_lights();
@@ -213,17 +218,26 @@ void ConeTraceRenderer::Render() {
     if (!check(vct_synchronize(ctx_), "sync")) return;
     last_ms_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     check(vct_memcpy(ctx_, &last_steps_, counter_, 8, 1), "read counter");
-    if (s_.has_sky) {   // the sky into the diffuse plane, once per frame, before whichever composite reads it
+    if (s_.has_sky || s_.has_env) {   // the sky into the diffuse plane, once per frame, before whichever composite reads it
         if (!sky_ && !check(vct_device_alloc(ctx_, (size_t)s_.width * s_.height * 16, &sky_), "alloc sky plane")) return;
-        check(vct_sky_cones_device(ctx_, a.pos4, a.nrm4, s_.width, s_.height, &s_.sky, (float*)sky_, a.diffuse4, nullptr),
-              "vct_sky_cones_device");
+        if (s_.has_env)
+            check(vct_env_cones_device(ctx_, a.pos4, a.nrm4, s_.width, s_.height, &s_.env, (float*)sky_, a.diffuse4, nullptr),
+                  "vct_env_cones_device");
+        else
+            check(vct_sky_cones_device(ctx_, a.pos4, a.nrm4, s_.width, s_.height, &s_.sky, (float*)sky_, a.diffuse4, nullptr),
+                  "vct_sky_cones_device");
     }
-    if (s_.has_sky && s_.sky_view && status_ == VCT_OK) {   // and into the specular plane
+    if ((s_.has_sky || s_.has_env) && s_.sky_view && status_ == VCT_OK) {   // and into the specular plane
         if (!sky_spec_ && !check(vct_device_alloc(ctx_, (size_t)s_.width * s_.height * 16, &sky_spec_), "alloc specular sky plane"))
             return;
-        check(vct_sky_specular_device(ctx_, a.pos4, a.nrm4, a.alb4, s_.width, s_.height, a.eye, &s_.sky, (float*)sky_spec_,
-                                      a.spec4, nullptr),
-              "vct_sky_specular_device");
+        if (s_.has_env)
+            check(vct_env_specular_device(ctx_, a.pos4, a.nrm4, a.alb4, s_.width, s_.height, a.eye, &s_.env,
+                                          (float*)sky_spec_, a.spec4, nullptr),
+                  "vct_env_specular_device");
+        else
+            check(vct_sky_specular_device(ctx_, a.pos4, a.nrm4, a.alb4, s_.width, s_.height, a.eye, &s_.sky,
+                                          (float*)sky_spec_, a.spec4, nullptr),
+                  "vct_sky_specular_device");
     }
     if (s_.temporal_len && status_ == VCT_OK) accumulate_diffuse();
 }
@@ -279,7 +293,9 @@ vct_status ConeTraceRenderer::composite(float* lin, uint32_t* rgba) {
 
 vct_status ConeTraceRenderer::composite_surface(float* lin, uint32_t* rgba) {
     const vct_status st = composite_terms(lin, rgba);
-    if (st != VCT_OK || !(s_.has_sky && s_.sky_view)) return st;
+    if (st != VCT_OK || !((s_.has_sky || s_.has_env) && s_.sky_view)) return st;
+    if (s_.has_env)
+        return vct_env_background_device(ctx_, &cam_, (const float*)gb_[0], s_.width, s_.height, &s_.env, lin, rgba);
     return vct_sky_background_device(ctx_, &cam_, (const float*)gb_[0], s_.width, s_.height, &s_.sky, lin, rgba);
 }
 

@@ -72,6 +72,14 @@ struct ConeTraceSettings {
     // plane after K4 (vct_sky_specular_device), and every composite is followed by
     // vct_sky_background_device, so the background shows the sky instead of the clear colour
     bool sky_view = false;
+    // an environment map (include/vct_env.h): env_size^2 RGBA float texels, octahedral, uploaded
+    // once with vct_set_env.  It takes the sky's place in every call above: vct_inject_env,
+    // vct_env_cones_device and, with sky_view, vct_env_specular_device and
+    // vct_env_background_device.  The default frame puts the map's +z at the world's +y
+    bool has_env = false;
+    std::vector<float> env_texels;
+    uint32_t env_size = 0;
+    vct_env_sky env = {{{1.0f, 0.0f, 0.0f}, {0.0f, 0.0f, -1.0f}, {0.0f, 1.0f, 0.0f}}, 1.0f};
     // model matrix applied to the model's vertices before K1, column-major; main.cpp
     // sets the reference's T(0,-1.75,0) S(0.2) (r_voxelization.cpp:26-29) by default
     float model[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};

@@ -34,8 +34,9 @@ from ._lib import VctFog
 from ._lib import VctTemporalArgs, VctTemporalParams
 from ._lib import VctCone, VctConeQueryArgs, VctProbeGrid
 from ._lib import VctVoxelPickArgs, VctVoxelViewArgs
+from ._lib import VctEnvSky
 
-__all__ = ["VctTemporalParams","Context", "VctError", "VctConfig", "VctCamera", "tiles_for_rank", "tile_offset", "VERTEX_FLOATS",
+__all__ = ["VctEnvSky", "env_sky", "VctTemporalParams","Context", "VctError", "VctConfig", "VctCamera", "tiles_for_rank", "tile_offset", "VERTEX_FLOATS",
            "VCT_ALL_RANKS", "comm_frame_layout", "VctLight", "directional_light", "point_light", "spot_light",
            "VctSky", "sky_light", "VctFog", "fog", "VctCone", "VctProbeGrid", "probe_grid", "VctMixedParams", "VctMixedHoles", "VCT_CONES_DIFFUSE", "VCT_CONES_SPECULAR"]
 
@@ -96,6 +97,17 @@ def sky_light(zenith, horizon=None, ground=None, up=(0.0, 1.0, 0.0)) -> VctSky:
     s.horizon = _f3(zenith if horizon is None else horizon)
     s.ground = _f3((0.0, 0.0, 0.0) if ground is None else ground)
     return s
+
+
+def env_sky(frame=((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0)), scale: float = 1.0) -> VctEnvSky:
+    """A vct_env_sky: `frame` holds the world directions of the map's x, y and z axes as rows
+    (world -> map), `scale` the intensity.  The library checks the record's input rule when a
+    call uses it."""
+    e = VctEnvSky()
+    for i, row in enumerate(frame):
+        e.frame[i] = _f3(row)
+    e.scale = float(scale)
+    return e
 
 
 def fog(density, albedo=(_lib.VCT_FOG_DEFAULT_ALBEDO,) * 3, ambient=0.0, level=_lib.VCT_FOG_DEFAULT_LEVEL,
@@ -654,6 +666,82 @@ class Context:
         self._check(fn(self.h, C.byref(cam), self._dev(pos4, "pos4", _F32, n), width, height, C.byref(sky),
                        self._dev(linear4_inout, "linear4_inout", _F32, n),
                        self._dev(rgba8_inout, "rgba8_inout", _I32, width * height)), "sky_background")
+
+    # -- the environment-map sky (include/vct_env.h) --------------------------
+    @staticmethod
+    def _env(env, what):
+        env = getattr(env, "record", env)            # a vct.env.EnvMap keeps its record
+        if not isinstance(env, VctEnvSky):
+            raise VctError(_EINVAL, f"{what}: expected a VctEnvSky (vct.env_sky) or a vct.env.EnvMap, got {type(env).__name__}")
+        return env
+
+    def set_env(self, oct4):
+        """vct_set_env: the context's octahedral map, [S, S, 4] float32 on the host (row 0 =
+        p.y = -1), S a power of two; None or an empty array clears it.  Synchronous."""
+        fn = _lib.bind_env_extension(self.lib, "vct_set_env")
+        if oct4 is None or np.asarray(oct4).size == 0:
+            self._check(fn(self.h, None, 0), "set_env")
+            return
+        m = np.ascontiguousarray(oct4, dtype=np.float32)
+        if m.ndim != 3 or m.shape[0] != m.shape[1] or m.shape[2] != 4:
+            raise VctError(_EINVAL, f"set_env: the map must be [S, S, 4] float32, got {m.shape}")
+        self._check(fn(self.h, _fptr(m), m.shape[0]), "set_env")
+
+    @property
+    def env_size(self) -> int:
+        return int(_lib.bind_env_extension(self.lib, "vct_env_size")(self.h))
+
+    def env_download_level(self, level: int) -> np.ndarray:
+        """vct_env_download_level: level `level` of the map's pyramid, [S_j, S_j, 4] float32."""
+        fn = _lib.bind_env_extension(self.lib, "vct_env_download_level")
+        sj = max(self.env_size >> level, 1)
+        out = np.empty((sj, sj, 4), np.float32)
+        self._check(fn(self.h, level, _fptr(out)), "env_download_level")
+        return out
+
+    def env_lookup_device(self, env, dir_tau4, count, out4):
+        """vct_env_lookup_device: (d.xyz, tau) per lane in dir_tau4 -> (Env.rgb, level m) in out4,
+        float32 device tensors of [count, 4]."""
+        fn = _lib.bind_env_extension(self.lib, "vct_env_lookup_device")
+        self._check(fn(self.h, C.byref(self._env(env, "env_lookup")), self._dev(dir_tau4, "dir_tau4", _F32, 4 * count),
+                       count, self._dev(out4, "out4", _F32, 4 * count)), "env_lookup")
+
+    def env_cones_device(self, pos4, nrm4, width, height, env, sky4, diffuse4_inout=None, cone_steps=None):
+        """vct_env_cones_device: sky_cones_device with the context's map for the sky colour."""
+        fn = _lib.bind_env_extension(self.lib, "vct_env_cones_device")
+        n = 4 * width * height
+        self._check(fn(self.h, self._dev(pos4, "pos4", _F32, n), self._dev(nrm4, "nrm4", _F32, n), width, height,
+                       C.byref(self._env(env, "env_cones")), self._dev(sky4, "sky4", _F32, n),
+                       self._dev(diffuse4_inout, "diffuse4_inout", _F32, n),
+                       self._dev(cone_steps, "cone_steps", _I64, 1)), "env_cones")
+
+    def inject_env(self, env):
+        """vct_inject_env: inject_sky with the map (one of the two, once per level 0)."""
+        fn = _lib.bind_env_extension(self.lib, "vct_inject_env")
+        self._check(fn(self.h, C.byref(self._env(env, "inject_env"))), "inject_env")
+
+    def env_specular_device(self, pos4, nrm4, alb4, width, height, eye, env, skyspec4, spec4_inout=None,
+                            cone_steps=None):
+        """vct_env_specular_device: sky_specular_device with the map, blurred by the pixel's aperture."""
+        fn = _lib.bind_env_extension(self.lib, "vct_env_specular_device")
+        n = 4 * width * height
+        self._check(fn(self.h, *self._gbuf_ptrs(width, height, pos4, nrm4, alb4), width, height, _f3(eye),
+                       C.byref(self._env(env, "env_specular")), self._dev(skyspec4, "skyspec4", _F32, n),
+                       self._dev(spec4_inout, "spec4_inout", _F32, n),
+                       self._dev(cone_steps, "cone_steps", _I64, 1)), "env_specular")
+
+    def env_background_device(self, cam, pos4, width, height, env, linear4_inout=None, rgba8_inout=None):
+        """vct_env_background_device: sky_background_device with Env(d, 0)."""
+        fn = _lib.bind_env_extension(self.lib, "vct_env_background_device")
+        if hasattr(cam, "to_ctypes"):
+            cam = cam.to_ctypes()
+        if not isinstance(cam, VctCamera):
+            raise VctError(_EINVAL, f"env_background: expected a camera, got {type(cam).__name__}")
+        n = 4 * width * height
+        self._check(fn(self.h, C.byref(cam), self._dev(pos4, "pos4", _F32, n), width, height,
+                       C.byref(self._env(env, "env_background")),
+                       self._dev(linear4_inout, "linear4_inout", _F32, n),
+                       self._dev(rgba8_inout, "rgba8_inout", _I32, width * height)), "env_background")
 
     # -- cone queries and the probe grid (include/vct_query.h) ---------------
     def cone_query_device(self, cones, count, out4, steps=None, cone_steps=None):

@@ -87,6 +87,12 @@ VCT_VOXHIT_FACE_INSIDE, VCT_VOXHIT_FACE_MISS, VCT_VOXHIT_CELL_MISS = 6, 7, 0xFFF
 VCT_VOXVIEW_SHADE = (0.8, 1.0, 0.6)          # VCT_VOXVIEW_SHADE_X / _Y / _Z (include/vct_spec.h)
 VCT_VOXVIEW_STEPS_PER_CELL = 3
 
+# include/vct_env.h: the environment-map sky, likewise HIP only (bind_env_extension)
+ENV_EXTENSIONS = ("vct_set_env", "vct_env_size", "vct_env_download_level", "vct_env_lookup_device",
+                  "vct_env_cones_device", "vct_inject_env", "vct_env_specular_device", "vct_env_background_device")
+VCT_ENV_MAX_DIM = 2048
+VCT_ENV_TEXEL_LIMIT = 2.0 ** 52
+
 STATUS = {0: "VCT_OK", 1: "VCT_EINVAL", 2: "VCT_ENOMEM", 3: "VCT_EDEVICE", 4: "VCT_ECOMM", 5: "VCT_ESTATE"}
 
 
@@ -137,6 +143,13 @@ class VctSky(C.Structure):            # vct_sky, 48 bytes
         ("zenith", C.c_float * 3),
         ("horizon", C.c_float * 3),
         ("ground", C.c_float * 3),
+    ]
+
+
+class VctEnvSky(C.Structure):         # vct_env_sky, 40 bytes
+    _fields_ = [
+        ("frame", (C.c_float * 3) * 3),
+        ("scale", C.c_float),
     ]
 
 
@@ -556,6 +569,32 @@ def bind_sky_view_extension(lib: C.CDLL, name: str):
     return fn
 
 
+def bind_env_extension(lib: C.CDLL, name: str):
+    """The include/vct_env.h function `name` of `lib`, with its signature declared;
+    AttributeError (naming the library) if this implementation does not export it."""
+    P, u32, i32 = C.c_void_p, C.c_uint32, C.c_int32
+    F3, E = C.POINTER(C.c_float), C.POINTER(VctEnvSky)
+    sig = {
+        "vct_set_env": (i32, [P, P, u32]),
+        "vct_env_size": (u32, [P]),
+        "vct_env_download_level": (i32, [P, u32, P]),
+        "vct_env_lookup_device": (i32, [P, E, P, u32, P]),
+        "vct_env_cones_device": (i32, [P, P, P, u32, u32, E, P, P, P]),
+        "vct_inject_env": (i32, [P, E]),
+        "vct_env_specular_device": (i32, [P, P, P, P, u32, u32, F3, E, P, P, P]),
+        "vct_env_background_device": (i32, [P, C.POINTER(VctCamera), P, u32, u32, E, P, P]),
+    }
+    res, args = sig[name]
+    try:
+        fn = getattr(lib, name)
+    except AttributeError:
+        raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
+                             "(include/vct_env.h is implemented by the HIP library only)") from None
+    fn.restype = res
+    fn.argtypes = args
+    return fn
+
+
 def bind_query_extension(lib: C.CDLL, name: str):
     """The include/vct_query.h function `name` of `lib`, with its signature declared;
     AttributeError (naming the library) if this implementation does not export it."""
@@ -705,6 +744,33 @@ def debug_sky_view_path(lib: C.CDLL, handle) -> int:
     """Test hook (vct_debug_sky_view_path): the address path the context's last specular sky
     march was launched with -- 32 (buffer resources), 64 (64-bit addresses), 0 before any."""
     fn = lib.vct_debug_sky_view_path
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p]
+    return int(fn(handle))
+
+
+def debug_env(lib: C.CDLL, force64: int = -1) -> None:
+    """Test and tool hook (vct_debug_env, not part of the headers).  force64 >= 0, process-wide:
+    nonzero sends every grid's env marches through the 64-bit-address path (the one 1024^3 takes)."""
+    fn = lib.vct_debug_env
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int]
+    fn(int(force64))
+
+
+def debug_env_mips(lib: C.CDLL, handle, profile: int = -1) -> float:
+    """Tool hook (vct_debug_env_mips).  profile >= 0: nonzero times the mip kernels of the
+    context's following set_env calls with events.  -> ms of the last timed build."""
+    fn = lib.vct_debug_env_mips
+    fn.restype = C.c_float
+    fn.argtypes = [C.c_void_p, C.c_int]
+    return float(fn(handle, int(profile)))
+
+
+def debug_env_path(lib: C.CDLL, handle) -> int:
+    """Test hook (vct_debug_env_path): the address path the context's last env march was
+    launched with: 32, 64, or 0 before the first one."""
+    fn = lib.vct_debug_env_path
     fn.restype = C.c_int
     fn.argtypes = [C.c_void_p]
     return int(fn(handle))
