@@ -40,6 +40,25 @@ int vcth_texture(const vcth_model* m, uint32_t i, const uint8_t** rgba8, uint32_
 /* Maps that failed to load, "path: reason" (TextureFromFile prints them, model.cpp:219-223). */
 uint32_t vcth_num_texture_errors(const vcth_model* m);
 const char* vcth_texture_error(const vcth_model* m, uint32_t i);
+/* The shading slots of material i (include/vct_shading.h; model.cpp:55-60 reads Ks, specularMaps
+ * and normalMaps).  Ns is the .mtl's Phong exponent (0 when absent).  Per slot the map_* path
+ * of the .mtl ("" = none) and its index in the model's SHADING texture list (-1: none, or it
+ * failed to load): map_Ks -> VCTH_MAP_SPECULAR; map_Kn -> VCTH_MAP_NORMAL, assimp 3.3's
+ * aiTextureType_NORMALS, the slot the reference reads; map_Bump / map_bump / bump ->
+ * VCTH_MAP_HEIGHT, which the reference never reads -- exposed so that a host may choose it as
+ * its normal map, as nanosuit's *_ddn.png in fact are.  These textures live in a list of their
+ * own, each path loaded once: vcth_num_textures, vcth_texture, vcth_material_diffuse_map and the
+ * diffuse list's errors are what they were. */
+#define VCTH_MAP_SPECULAR 0
+#define VCTH_MAP_NORMAL   1
+#define VCTH_MAP_HEIGHT   2
+int vcth_material_shininess(const vcth_model* m, uint32_t i, float* ns);
+int vcth_material_shading_map(const vcth_model* m, uint32_t i, int slot, const char** path, int32_t* texture);
+uint32_t vcth_num_shading_textures(const vcth_model* m);
+int vcth_shading_texture(const vcth_model* m, uint32_t i, const uint8_t** rgba8, uint32_t* width, uint32_t* height,
+                         const char** path);
+uint32_t vcth_num_shading_texture_errors(const vcth_model* m);
+const char* vcth_shading_texture_error(const vcth_model* m, uint32_t i);
 /* PNG decode as stbi_load(file, &w, &h, &comp, 0) (model.cpp:197): *data = h rows of
  * w * comp bytes (release with vcth_free_image).  Returns 0, or -1 with a message. */
 int vcth_decode_png(const uint8_t* file, size_t bytes, uint8_t** data, uint32_t* width, uint32_t* height, int* comp,

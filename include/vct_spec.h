@@ -888,4 +888,52 @@
  *    s_dn = c for finite s).
  *  The section's literal (VCT_ENV_TEXEL_LIMIT) stands with VCT_COLOR_LIMIT, above. */
 
+/* ---- shading attributes (vct_set_shading / vct_gbuffer_shaded_device /
+ * vct_specular_tint_device, include/vct_shading.h; tests/shading_ref.py restates it) ----------
+ *  Input rule, vct_set_shading.  VCT_ESTATE without a voxelization.  VCT_EINVAL, the previous
+ *    set kept: NULL verts, idx or materials, n_materials == 0; n_idx != 3 x the static
+ *    voxelization's triangles (a dynamic layer's are not counted); an idx[i] >= n_verts; a
+ *    present offset (!= VCT_SHADING_NO_ATTR) that is not a multiple of 4 or with offset + size
+ *    > vertex_stride (size 12 for normal, tangent, bitangent; 8 for uv); tri_material[t] >=
+ *    n_materials; a ks component not finite, with its sign bit set, or > VCT_COLOR_LIMIT (the
+ *    colour rule of "K2 input rule"); roughness not in [0, 1] (a NaN fails the compare); a map
+ *    index < -1 or >= the texture count of the moment; a flag bit other than
+ *    VCT_SHADING_FLIP_GREEN; reserved != 0.  Vertex attribute contents are data, never a status.
+ *    The set belongs to the static triangles: vct_voxelize* and vct_load_grid drop it,
+ *    vct_voxelize_dynamic* keeps it.
+ *  Input rule, vct_gbuffer_shaded_device.  The "G-buffer input rule" on the camera and the frame;
+ *    pos4, nrm4, alb4, ks4 not NULL and 16-byte aligned; geo4 (16), tri_id (4), bary2 (8 bytes)
+ *    aligned when given: VCT_EINVAL, nothing written.  VCT_ESTATE without a set.
+ *  The pixel.  Each written operation rounds once; fmaf appears only where written; dot3(a, b) =
+ *    (a.x b.x + a.y b.y) + a.z b.z.  The hit (k, t), pos4, the depth test and the background
+ *    texel are vct_gbuffer_raster_device's in every bit.  For a hit on triangle k < the set's
+ *    triangle count, with the unit ray direction d:
+ *    1. (b1, b2) = the Moller-Trumbore (u, v) of the hit (ray_tri_bary: the operations of the
+ *       intersection test).  An attribute a with vertex values a0, a1, a2 interpolates as
+ *         a = fmaf(b2, a2 - a0, fmaf(b1, a1 - a0, a0))            ("diffuse maps"' TexCoords form)
+ *    2. Ng = the face normal as the raster pass computes and flips it: n = e1 x e2, n / sqrtf(
+ *       dot3(n, n)) per component, negated when dot3(n, d) > 0; `flipped` = it was negated.
+ *    3. unit(v) = v / sqrtf(dot3(v, v)) per component, defined where dot3(v, v) is finite and
+ *       > 0.  N0 = unit(interpolated Normal), negated when flipped; N0 = Ng when the normal
+ *       attribute is absent or unit() is not defined.
+ *    4. If the material's normal_map is >= 0 and < the CURRENT texture count, and the uv, tangent
+ *       and bitangent attributes are present: c = T_map(u, v) ("diffuse maps", rgb);
+ *       m = fmaf(2.0f, c, -1.0f) per channel, m.y = -m.y under VCT_SHADING_FLIP_GREEN; T, B = the
+ *       interpolated Tangent and Bitangent (not re-orthogonalised), negated when flipped;
+ *         N1 = unit((m.x T + m.y B) + m.z N0)  per component,   N1 = N0 where unit() is not defined.
+ *       Otherwise N1 = N0.
+ *    5. N = N1 if dot3(N1, d) < 0, else Ng: a shading normal never faces away from the viewer.
+ *    6. nrm4 = (N, 0); geo4 = (Ng, 0); alb4 = (Kd x T_diffuse as the raster pass, the material's
+ *       roughness); ks4 = (Ks_c * T_specular(u, v)_c, 1) where the material's specular_map is
+ *       >= 0 and < the current texture count and uv is present, else (Ks, 1); tri_id = k;
+ *       bary2 = (b1, b2).
+ *    7. A hit outside the set (a dynamic-layer triangle) is the flat record: nrm4 = geo4 = (Ng, 0),
+ *       alb4.w = the call's roughness, ks4 = (1, 1, 1, 1); tri_id and bary2 as in 6.
+ *    8. Background: pos4 = nrm4 = geo4 = ks4 = 0, alb4 = (0, 0, 0, roughness), tri_id =
+ *       0xFFFFFFFF, bary2 = 0.
+ *    With every attribute absent and every material's roughness the call's, pos4, nrm4 and alb4
+ *    equal vct_gbuffer_raster_device's in every bit.
+ *  vct_specular_tint_device: out.rgb = spec.rgb * ks.rgb, out.a = spec.a; contents are data.
+ *  No new literal. */
+
 #endif /* VCT_SPEC_H */

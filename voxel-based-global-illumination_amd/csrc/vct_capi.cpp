@@ -334,6 +334,7 @@ void vct_destroy(vct_ctx* c) {
     dynamic_free(c);
     fog_free(c);
     env_free(c);
+    shading_free(c);
     for (auto& s : c->scratch)
         if (s.p) (void)hipFree(s.p);
     for (auto& ss : c->k4s)

@@ -344,7 +344,9 @@ vct_status dynamic_update(vct_ctx* c, const void* d_verts, uint32_t stride, uint
     g.voxelized = g.injected = g.mipped = g.bounced = g.emitted = g.skied = false;
     g.k2_coarse_ok = g.k3_sparse_ok = g.zm_valid = false;
     g.k3_live_bz = 0;
+    const bool shaded = shading_live(c);   // the shading set describes the static triangles, which stay
     ++c->grid_epoch;
+    if (shaded) c->shade.epoch = c->grid_epoch;
     d.live = false;
     m.n_tri = n_static;
     if (!had) {   // no layer in place: whatever the record sets hold belongs to an earlier grid

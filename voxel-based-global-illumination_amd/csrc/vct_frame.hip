@@ -7,6 +7,7 @@
 //    r_voxelization.cpp:18): vertical FOV = Zoom, aspect w/h, near 0.1, far 100.
 #include "vct_internal.h"
 #include "vct_view.h"
+#include "vct_gbuffer.h"
 
 namespace vct {
 namespace {
@@ -43,51 +44,7 @@ __global__ void __launch_bounds__(256) k_untile(const UntileK k) {
 }
 
 // ---- G-buffer ray caster (input producer for synthetic scenes) -----------
-struct RayK {
-    const float4* tri;  // [n][4]: v0, e1, e2, (kd, diffuse map as int bits)
-    const float4* uv;   // [n][2] TexCoords of textured triangles (NULL: untextured voxelization)
-    const uint32_t* texels;   // diffuse maps (vct_set_textures)
-    const TexDesc* tdesc;
-    uint32_t n_tex;
-    uint32_t n_tri;
-    int w, h;
-    float px, py, pz;
-    float fx, fy, fz, ux, uy, uz, rx, ry, rz;
-    float tan_half, aspect, near_p, far_p, rough;
-    float4* pos;
-    float4* nrm;
-    float4* alb;
-};
-
-constexpr int kRayChunk = 256;
-
-// Moller-Trumbore: ray parameter t of the hit, or -1 (no hit / parallel)
-__device__ __forceinline__ float ray_tri(float4 v0, float4 e1, float4 e2, float px, float py, float pz, float dx,
-                                         float dy, float dz) {
-    const float pvx = dy * e2.z - dz * e2.y, pvy = dz * e2.x - dx * e2.z, pvz = dx * e2.y - dy * e2.x;
-    const float det = dot3(e1.x, e1.y, e1.z, pvx, pvy, pvz);
-    if (fabsf(det) < 1e-12f) return -1.0f;
-    const float inv = 1.0f / det;
-    const float tx = px - v0.x, ty = py - v0.y, tz = pz - v0.z;
-    const float u = dot3(tx, ty, tz, pvx, pvy, pvz) * inv;
-    if (u < 0.0f || u > 1.0f) return -1.0f;
-    const float qx = ty * e1.z - tz * e1.y, qy = tz * e1.x - tx * e1.z, qz = tx * e1.y - ty * e1.x;
-    const float v = dot3(dx, dy, dz, qx, qy, qz) * inv;
-    if (v < 0.0f || u + v > 1.0f) return -1.0f;
-    return dot3(e2.x, e2.y, e2.z, qx, qy, qz) * inv;
-}
-
-// Moller-Trumbore barycentrics (u, v) of a ray known to hit the triangle (ray_tri's operations)
-__device__ __forceinline__ void ray_tri_bary(float4 v0, float4 e1, float4 e2, float px, float py, float pz, float dx,
-                                             float dy, float dz, float& u, float& v) {
-    const float pvx = dy * e2.z - dz * e2.y, pvy = dz * e2.x - dx * e2.z, pvz = dx * e2.y - dy * e2.x;
-    const float det = dot3(e1.x, e1.y, e1.z, pvx, pvy, pvz);
-    const float inv = 1.0f / det;
-    const float tx = px - v0.x, ty = py - v0.y, tz = pz - v0.z;
-    u = dot3(tx, ty, tz, pvx, pvy, pvz) * inv;
-    const float qx = ty * e1.z - tz * e1.y, qy = tz * e1.x - tx * e1.z, qz = tx * e1.y - ty * e1.x;
-    v = dot3(dx, dy, dz, qx, qy, qz) * inv;
-}
+// RayK, ray_tri and ray_tri_bary are vct_gbuffer.h's, shared with vct_shading.hip
 
 // pixel_ray (pixel -> unit ray direction) is vct_view.h's, shared with vct_fog.hip
 
@@ -159,20 +116,9 @@ __global__ void __launch_bounds__(256) k_raycast(RayK k) {
 // triangle a ray of the tile can hit at any depth: nothing is culled against
 // far_plane, a triangle that can be hit nearer than kZc gets the whole frame, and
 // a box grows with the triangle's conditioning (an edge-on one: the whole frame).
-constexpr int kGT = 16;
 constexpr float kZc = 1e-5f;
 
-struct BinK {
-    RayK r;
-    int tiles_x, tiles_y;
-    float sxs, sys;                // pixel scale: X = w/2 + (cx/cz) sxs, Y = h/2 - (cy/cz) sys
-    float t_near;                  // 2 kZc max|D|: a hit with cz < kZc has a ray parameter below half of this
-    float pad;                     // 2^-20 s M^2: pixels of float32 slack per unit of a triangle's conditioning
-    int4* rect;                    // per triangle tile rectangle (x0 > x1: culled)
-    uint32_t* count;               // per tile: triangles, then the fill cursor
-    uint32_t* offset;              // per tile: exclusive prefix of count; [n_tiles] = total
-    uint32_t* bins;                // triangle indices grouped by tile
-};
+// (BinK is vct_gbuffer.h's)
 
 __global__ void __launch_bounds__(256) k_bin_rect(BinK k) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
@@ -420,9 +366,9 @@ hipError_t launch_raycast(vct_ctx* c, const vct_camera* cam, uint32_t w, uint32_
     return hipGetLastError();
 }
 
-hipError_t launch_gbuffer_binned(vct_ctx* c, const vct_camera* cam, uint32_t w, uint32_t h, float rough,
-                                 float4* pos, float4* nrm, float4* alb) {
-    BinK k;
+hipError_t gbuffer_bins(vct_ctx* c, const vct_camera* cam, uint32_t w, uint32_t h, float rough, float4* pos,
+                        float4* nrm, float4* alb, BinK* out) {
+    BinK& k = *out;
     k.r = ray_params(c, cam, w, h, rough, pos, nrm, alb);
     k.tiles_x = (int)((w + kGT - 1) / kGT);
     k.tiles_y = (int)((h + kGT - 1) / kGT);
@@ -451,7 +397,15 @@ hipError_t launch_gbuffer_binned(vct_ctx* c, const vct_camera* cam, uint32_t w, 
     if ((e = scratch_get(c, 3, (size_t)(total ? total : 1) * 4, &sp)) != hipSuccess) return e;
     k.bins = (uint32_t*)sp;
     if (n_tri && total) hipLaunchKernelGGL(k_bin_fill, dim3(tb), dim3(256), 0, c->stream, k);
-    hipLaunchKernelGGL(k_bin_raster, dim3(n_tiles), dim3(256), 0, c->stream, k);
+    return hipGetLastError();
+}
+
+hipError_t launch_gbuffer_binned(vct_ctx* c, const vct_camera* cam, uint32_t w, uint32_t h, float rough,
+                                 float4* pos, float4* nrm, float4* alb) {
+    BinK k;
+    const hipError_t e = gbuffer_bins(c, cam, w, h, rough, pos, nrm, alb, &k);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_bin_raster, dim3((uint32_t)(k.tiles_x * k.tiles_y)), dim3(256), 0, c->stream, k);
     return hipGetLastError();
 }
 

@@ -1,0 +1,80 @@
+// vct_gbuffer.h — what the G-buffer passes of vct_frame.hip and the shaded pass of
+// vct_shading.hip share: the kernel records, the Moller-Trumbore test and its barycentrics.
+// One definition each, so the passes cannot drift apart.  Internal to the including
+// translation unit.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "vct_internal.h"
+
+namespace vct {
+
+// ---- G-buffer ray caster (input producer for synthetic scenes) -----------
+struct RayK {
+    const float4* tri;  // [n][4]: v0, e1, e2, (kd, diffuse map as int bits)
+    const float4* uv;   // [n][2] TexCoords of textured triangles (NULL: untextured voxelization)
+    const uint32_t* texels;   // diffuse maps (vct_set_textures)
+    const TexDesc* tdesc;
+    uint32_t n_tex;
+    uint32_t n_tri;
+    int w, h;
+    float px, py, pz;
+    float fx, fy, fz, ux, uy, uz, rx, ry, rz;
+    float tan_half, aspect, near_p, far_p, rough;
+    float4* pos;
+    float4* nrm;
+    float4* alb;
+};
+
+constexpr int kRayChunk = 256;
+constexpr int kGT = 16;   // pixels per side of a bin tile
+
+struct BinK {
+    RayK r;
+    int tiles_x, tiles_y;
+    float sxs, sys;                // pixel scale: X = w/2 + (cx/cz) sxs, Y = h/2 - (cy/cz) sys
+    float t_near;                  // 2 kZc max|D|: a hit with cz < kZc has a ray parameter below half of this
+    float pad;                     // 2^-20 s M^2: pixels of float32 slack per unit of a triangle's conditioning
+    int4* rect;                    // per triangle tile rectangle (x0 > x1: culled)
+    uint32_t* count;               // per tile: triangles, then the fill cursor
+    uint32_t* offset;              // per tile: exclusive prefix of count; [n_tiles] = total
+    uint32_t* bins;                // triangle indices grouped by tile
+};
+
+// The binned pass up to its last launch (vct_frame.hip): the bins of the frame, queued on the
+// ctx stream (one 4-byte read back); *k is ready for a raster kernel over k->tiles_x *
+// k->tiles_y workgroups
+hipError_t gbuffer_bins(vct_ctx* c, const vct_camera* cam, uint32_t w, uint32_t h, float rough, float4* pos,
+                        float4* nrm, float4* alb, BinK* k);
+
+namespace {
+
+// Moller-Trumbore: ray parameter t of the hit, or -1 (no hit / parallel)
+__device__ __forceinline__ float ray_tri(float4 v0, float4 e1, float4 e2, float px, float py, float pz, float dx,
+                                         float dy, float dz) {
+    const float pvx = dy * e2.z - dz * e2.y, pvy = dz * e2.x - dx * e2.z, pvz = dx * e2.y - dy * e2.x;
+    const float det = dot3(e1.x, e1.y, e1.z, pvx, pvy, pvz);
+    if (fabsf(det) < 1e-12f) return -1.0f;
+    const float inv = 1.0f / det;
+    const float tx = px - v0.x, ty = py - v0.y, tz = pz - v0.z;
+    const float u = dot3(tx, ty, tz, pvx, pvy, pvz) * inv;
+    if (u < 0.0f || u > 1.0f) return -1.0f;
+    const float qx = ty * e1.z - tz * e1.y, qy = tz * e1.x - tx * e1.z, qz = tx * e1.y - ty * e1.x;
+    const float v = dot3(dx, dy, dz, qx, qy, qz) * inv;
+    if (v < 0.0f || u + v > 1.0f) return -1.0f;
+    return dot3(e2.x, e2.y, e2.z, qx, qy, qz) * inv;
+}
+
+// Moller-Trumbore barycentrics (u, v) of a ray known to hit the triangle (ray_tri's operations)
+__device__ __forceinline__ void ray_tri_bary(float4 v0, float4 e1, float4 e2, float px, float py, float pz, float dx,
+                                             float dy, float dz, float& u, float& v) {
+    const float pvx = dy * e2.z - dz * e2.y, pvy = dz * e2.x - dx * e2.z, pvz = dx * e2.y - dy * e2.x;
+    const float det = dot3(e1.x, e1.y, e1.z, pvx, pvy, pvz);
+    const float inv = 1.0f / det;
+    const float tx = px - v0.x, ty = py - v0.y, tz = pz - v0.z;
+    u = dot3(tx, ty, tz, pvx, pvy, pvz) * inv;
+    const float qx = ty * e1.z - tz * e1.y, qy = tz * e1.x - tx * e1.z, qz = tx * e1.y - ty * e1.x;
+    v = dot3(dx, dy, dz, qx, qy, qz) * inv;
+}
+
+}  // namespace
+}  // namespace vct

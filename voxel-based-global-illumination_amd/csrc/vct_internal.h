@@ -212,6 +212,22 @@ struct Env {
     float mip_ms = 0.0f;             // the mip kernels of the last timed vct_set_env
 };
 
+// The shading set (vct_shading.hip; vct_spec.h "shading attributes").  Per static triangle one
+// record of nine float4 -- per vertex k (normal_k, u_k), (tangent_k, v_k), (bitangent_k, word_k)
+// with word_0 = the material index, word_1 = the kShade* presence bits, word_2 = 0 -- so every
+// fetch of the pass is one 16-byte load, and the material table as the host gave it (32 bytes a
+// material).  It belongs to the static triangles of the voxelization `epoch`; a dynamic update
+// carries a live set over to its new epoch (vct_dynamic.hip), every other voxelization or load
+// drops it.
+struct Shading {
+    float4* rec = nullptr;           // [n_tri][9]
+    float4* mats = nullptr;          // [n_mat][2]
+    size_t rec_cap = 0, mat_cap = 0; // bytes
+    uint32_t n_tri = 0, n_mat = 0;
+    bool live = false;
+    uint32_t epoch = 0;
+};
+
 // K4's per-launch scratch, one set per stream: K4 launches on different streams may run
 // concurrently (a host that overlaps consecutive frames), so the cone-split hand-over
 // and the ray-reorder buffers belong to the stream, not to the context.
@@ -345,6 +361,7 @@ struct vct_ctx {
     vct::Dynamic dyn;                   // dynamic layer of vct_voxelize_dynamic*
     vct::Fog fog;                       // scatter volume of vct_build_fog
     vct::Env env;                       // map and mips of vct_set_env
+    vct::Shading shade;                 // attribute records and materials of vct_set_shading
     uint32_t grid_epoch = 0;            // bumped by every voxelization (a new scene for the tuner)
     vct::StepRow* step_tab = nullptr;   // [kMaxStepRows] diffuse-cone step table (device)
     unsigned* spec_keys = nullptr;      // [2 * kSpecSlots]: specular table keys (~0u free), then states
@@ -514,6 +531,10 @@ inline bool fog_current(const vct_ctx* c) {
 void fog_free(vct_ctx* c);
 // environment-map sky (vct_env.hip): release with the context
 void env_free(vct_ctx* c);
+// shading set (vct_shading.hip): the context holds one for the current static triangles;
+// release with the context
+inline bool shading_live(const vct_ctx* c) { return c->shade.live && c->shade.epoch == c->grid_epoch; }
+void shading_free(vct_ctx* c);
 // ray reordering (variant 0x8000, vct_reorder.hip): *perm = the frame's pixels sorted by the
 // Morton code of their cone origin's voxel, background last (device, w * h entries)
 // (perm_spec, nullable: a second order for the specular part, by cell and cone aperture)

@@ -46,6 +46,11 @@
 //            the frame's camera through pyramid level LEVEL is written next to the frame as
 //            <out stem>.voxels<LEVEL>-<MODE>.png, shaded by entry face.  MODE: radiance (default),
 //            alpha, albedo or normal; albedo and normal exist at level 0 only;
+//   --shaded: the shading G-buffer (include/vct_shading.h): the loader's vertex normals, tangents and
+//            bitangents, each material's Ks, Ns (as roughness sqrt(2 / (Ns + 2))), map_Ks and normal
+//            map (map_Kn, else the map_Bump / bump slot) go through vct_set_shading and
+//            vct_gbuffer_shaded_device, and vct_specular_tint_device tints the specular plane before
+//            the composite; absent: face normals, one roughness, an untinted specular plane;
 //   --dynamic: a second model, voxelized as the context's dynamic layer (include/vct_dynamic.h)
 //            on top of the first one's grid; Kd materials only (its diffuse maps are not loaded).
 //            --dynamic-offset: a world-space translation applied after the model matrix of
@@ -230,7 +235,7 @@ int main(int argc, char** argv) {
     std::string linear;
     std::vector<vct_light> lights;
     float shadow_tan = 0.0f;
-    bool has_sky = false, sky_view = false;
+    bool has_sky = false, sky_view = false, shaded = false;
     vct_sky sky{};
     bool has_env = false;
     std::vector<float> env_texels;
@@ -264,6 +269,7 @@ int main(int argc, char** argv) {
             has_sky = true;
         }
         else if (a == "--sky-view") sky_view = true;
+        else if (a == "--shaded") shaded = true;
         else if (a == "--env" || a.rfind("--env=", 0) == 0) {
             const std::string spec = a == "--env" ? (i + 1 < argc ? argv[++i] : "") : a.substr(6);
             std::string why;
@@ -332,7 +338,7 @@ int main(int argc, char** argv) {
     if (sky_view && !has_sky && !has_env) { std::fprintf(stderr, "--sky-view needs --sky Z[:H[:G]] or --env FILE[:SCALE]\n"); return 2; }
     if (pos.empty()) {
         std::fprintf(stderr, "usage: %s model.obj [grid] [width] [height] [frames] [out.ppm] [devices] "
-                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] [--sky Z[:H[:G]]] [--env FILE[:SCALE]] [--sky-view] [--mixed 2|4] [--fog DENSITY] [--temporal N] [--probes D] [--voxels LEVEL[:MODE]]... "
+                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] [--sky Z[:H[:G]]] [--env FILE[:SCALE]] [--sky-view] [--shaded] [--mixed 2|4] [--fog DENSITY] [--temporal N] [--probes D] [--voxels LEVEL[:MODE]]... "
                              "[--dynamic FILE.obj [--dynamic-offset x,y,z]] "
                              "[--light dir:d:rgb | point:p:rgb:range | spot:p:d:rgb:range:inner:outer]...\n",
                      argv[0]);
@@ -355,6 +361,7 @@ int main(int argc, char** argv) {
     s.has_sky = has_sky;
     s.sky = sky;
     s.sky_view = sky_view;
+    s.shaded = shaded;
     s.has_env = has_env;
     s.env_texels = std::move(env_texels);
     s.env_size = env_size;

@@ -50,6 +50,7 @@ ConeTraceRenderer::~ConeTraceRenderer() {
     if (vis_) vct_device_free(ctx_, vis_);
     if (sky_) vct_device_free(ctx_, sky_);
     if (sky_spec_) vct_device_free(ctx_, sky_spec_);
+    if (ks_) vct_device_free(ctx_, ks_);
     if (fog_) vct_device_free(ctx_, fog_);
     for (void* p : {probes_, probe_state_, probe_plane_}) if (p) vct_device_free(ctx_, p);
     for (void* p : hist_) if (p) vct_device_free(ctx_, p);
@@ -78,6 +79,10 @@ bool ConeTraceRenderer::rebuild_scene() {
     // the diffuse maps (Model::loadMaterialTextures): albedo = Kd x map in K1 and the G-buffer
     std::vector<vct_texture> tex;
     for (const Texture& t : model->textures) tex.push_back(vct_texture{t.rgba.data(), t.width, t.height});
+    // the shading maps follow the diffuse ones in the one texture set (shaded)
+    const int32_t shading_base = (int32_t)tex.size();
+    if (s_.shaded)
+        for (const Texture& t : model->shading_textures) tex.push_back(vct_texture{t.rgba.data(), t.width, t.height});
     if (!check(vct_set_textures(ctx_, tex.data(), (uint32_t)tex.size()), "vct_set_textures")) return false;
     const std::vector<int32_t> map = model->MaterialMap();
     if (!check(vct_voxelize_textured(ctx_, v.data(), sizeof(Vertex), (uint32_t)v.size(), idx.data(),
@@ -85,6 +90,28 @@ bool ConeTraceRenderer::rebuild_scene() {
                                      (uint32_t)(kd4.size() / 4), (uint32_t)offsetof(Vertex, TexCoords)),
                "vct_voxelize_textured"))
         return false;
+    if (s_.shaded) {
+        // Material::Ks, Ns as a roughness, the specular map, and as the normal map the slot the
+        // reference reads (map_Kn) or else the height slot (nanosuit's *_ddn.png are normal maps)
+        std::vector<vct_shading_material> mats;
+        for (const Material& mt : model->materials) {
+            vct_shading_material sm{};
+            for (int k = 0; k < 3; ++k) sm.ks[k] = mt.Ks[k];
+            sm.roughness = std::min(1.0f, std::max(0.0f, std::sqrt(2.0f / (mt.Ns + 2.0f))));
+            const int nm = mt.shadingMaps[kMapNormal] >= 0 ? mt.shadingMaps[kMapNormal] : mt.shadingMaps[kMapHeight];
+            sm.normal_map = nm >= 0 ? shading_base + nm : -1;
+            sm.specular_map = mt.shadingMaps[kMapSpecular] >= 0 ? shading_base + mt.shadingMaps[kMapSpecular] : -1;
+            mats.push_back(sm);
+        }
+        vct_shading_desc d{};
+        d.verts = v.data(); d.vertex_stride = sizeof(Vertex); d.n_verts = (uint32_t)v.size();
+        d.idx = idx.data(); d.n_idx = (uint32_t)idx.size();
+        d.tri_material = tri_mat.data();
+        d.normal_offset = (uint32_t)offsetof(Vertex, Normal); d.uv_offset = (uint32_t)offsetof(Vertex, TexCoords);
+        d.tangent_offset = (uint32_t)offsetof(Vertex, Tangent); d.bitangent_offset = (uint32_t)offsetof(Vertex, Bitangent);
+        d.materials = mats.data(); d.n_materials = (uint32_t)mats.size();
+        if (!check(vct_set_shading(ctx_, &d), "vct_set_shading")) return false;
+    }
     scene_dirty_ = false;
     dynamic_dirty_ = true;              // a voxelization drops the layer: put it back before the light
     if (!s_.dynamic_model.empty()) return update_dynamic();
@@ -192,9 +219,15 @@ void ConeTraceRenderer::Render() {
         std::swap(gb_[0], prev_gb_[0]);
         std::swap(gb_[1], prev_gb_[1]);
     }
-    if (!check(vct_gbuffer_raster_device(ctx_, &vc, s_.width, s_.height, s_.roughness, (float*)gb_[0],
-                                         (float*)gb_[1], (float*)gb_[2]), "G-buffer"))
+    if (s_.shaded) {
+        if (!ks_ && !check(vct_device_alloc(ctx_, (size_t)s_.width * s_.height * 16, &ks_), "alloc ks plane")) return;
+        if (!check(vct_gbuffer_shaded_device(ctx_, &vc, s_.width, s_.height, s_.roughness, (float*)gb_[0], (float*)gb_[1],
+                                             (float*)gb_[2], (float*)ks_, nullptr, nullptr, nullptr), "shaded G-buffer"))
+            return;
+    } else if (!check(vct_gbuffer_raster_device(ctx_, &vc, s_.width, s_.height, s_.roughness, (float*)gb_[0],
+                                                (float*)gb_[1], (float*)gb_[2]), "G-buffer")) {
         return;
+    }
     unsigned long long zero = 0;
     if (!check(vct_memcpy(ctx_, counter_, &zero, 8, 0), "reset counter")) return;
     vct_trace_args a{};
@@ -239,6 +272,9 @@ void ConeTraceRenderer::Render() {
                                           (float*)sky_spec_, a.spec4, nullptr),
                   "vct_sky_specular_device");
     }
+    // the tint goes before any composite, and after everything that adds to the specular plane
+    if (s_.shaded && status_ == VCT_OK)
+        check(vct_specular_tint_device(ctx_, a.spec4, (const float*)ks_, s_.width, s_.height, a.spec4), "vct_specular_tint_device");
     if (s_.temporal_len && status_ == VCT_OK) accumulate_diffuse();
 }
 

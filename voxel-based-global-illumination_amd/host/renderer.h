@@ -72,6 +72,9 @@ struct ConeTraceSettings {
     // plane after K4 (vct_sky_specular_device), and every composite is followed by
     // vct_sky_background_device, so the background shows the sky instead of the clear colour
     bool sky_view = false;
+    // the shading G-buffer (include/vct_shading.h): vertex normals, normal and specular maps, Ks and
+    // a roughness per material from the loader, and the specular plane tinted by Ks x map_Ks
+    bool shaded = false;
     // an environment map (include/vct_env.h): env_size^2 RGBA float texels, octahedral, uploaded
     // once with vct_set_env.  It takes the sky's place in every call above: vct_inject_env,
     // vct_env_cones_device and, with sky_view, vct_env_specular_device and
@@ -134,6 +137,7 @@ private:
     void* vis_ = nullptr;                 // V planes of the soft-shadow composite (shadow_tan > 0), kept
     size_t vis_bytes_ = 0;
     void* sky_ = nullptr;                 // (Sk.rgb, vis) plane of the frame's sky call (has_sky), kept
+    void* ks_ = nullptr;                  // (Ks x map_Ks, 1) plane of the shaded G-buffer pass (shaded), kept
     void* sky_spec_ = nullptr;            // (S.rgb, T) plane of the frame's specular sky call (sky_view), kept
     void* probes_ = nullptr;              // probes, states and the sampled plane of the probe grid (probes > 0), kept
     void* probe_state_ = nullptr;

@@ -159,6 +159,13 @@ void load_mtl(const std::string& path, std::vector<Material>& mats) {
             // texture options (-clamp on, -o u v w, ...) are skipped, the rest of the line
             // is the file name
             cur->diffuse_map = texture_name(rest_of_line(ss));
+        } else if (cur && tag == "Ns") {
+            read_floats(ss, &cur->Ns, 1);
+        } else if (cur && (tag == "map_Ks" || tag == "map_Kn" || tag == "map_Bump" || tag == "map_bump" || tag == "bump")) {
+            // the shading slots: map_Ks specular, map_Kn normal (aiTextureType_NORMALS in assimp
+            // 3.3), map_Bump / map_bump / bump height; a later statement replaces the slot
+            const int slot = tag == "map_Ks" ? kMapSpecular : (tag == "map_Kn" ? kMapNormal : kMapHeight);
+            cur->shading_map[slot] = texture_name(rest_of_line(ss));
         }
     }
 }
@@ -529,7 +536,39 @@ bool Model::LoadObj(const std::string& path, std::string* err, bool load_texture
         }
     }
     if (load_textures) LoadTextures();
+    if (load_textures) LoadShadingTextures();
     return true;
+}
+
+void Model::LoadShadingTextures() {
+    static const char* const kType[3] = {"texture_specular", "texture_normal", "texture_height"};
+    shading_textures.clear();
+    shading_texture_errors.clear();
+    for (Material& mt : materials)
+        for (int slot = 0; slot < 3; ++slot) {
+            mt.shadingMaps[slot] = -1;
+            const std::string& name = mt.shading_map[slot];
+            if (name.empty()) continue;
+            int found = -1;
+            for (size_t j = 0; j < shading_textures.size(); ++j)
+                if (shading_textures[j].path == name) { found = (int)j; break; }
+            if (found < 0) {
+                PngImage img;
+                Texture t;
+                std::string e;
+                if (!LoadPng(directory + '/' + name, &img, &e) || !ExpandToRgba(img, &t.rgba, &e)) {
+                    shading_texture_errors.push_back(name + ": " + e);
+                    continue;
+                }
+                t.type = kType[slot];
+                t.path = name;
+                t.width = img.width;
+                t.height = img.height;
+                shading_textures.push_back(std::move(t));
+                found = (int)shading_textures.size() - 1;
+            }
+            mt.shadingMaps[slot] = found;
+        }
 }
 
 void Model::LoadTextures() {

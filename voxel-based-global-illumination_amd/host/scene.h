@@ -40,7 +40,15 @@ struct Material {                  // material.h:5-18
     std::array<float, 4> Ks{0, 0, 0, 1};
     std::string diffuse_map;       // map_Kd of the .mtl ("" = none); the only map the VCT path reads
     std::vector<int> diffuseMaps;  // indices into Model::textures (loadMaterialTextures, model.cpp:57)
+    // the shading slots (model.cpp:55-60: Ks, specularMaps, normalMaps): Ns, and per slot the
+    // map_* path of the .mtl ("" = none) and its index in Model::shading_textures (-1: none,
+    // or it failed to load).  map_Kn is assimp 3.3's aiTextureType_NORMALS, the slot the
+    // reference reads; map_Bump / bump is the height slot, which it never reads
+    float Ns = 0.0f;
+    std::string shading_map[3];    // kMapSpecular, kMapNormal, kMapHeight
+    int shadingMaps[3] = {-1, -1, -1};
 };
+enum { kMapSpecular = 0, kMapNormal = 1, kMapHeight = 2 };
 
 struct Mesh {                      // mesh.h:7-26 CPU copies (vertices, indices, material)
     std::vector<Vertex> vertices;
@@ -55,6 +63,10 @@ public:
     std::vector<Texture> textures;   // model.h `textures`: every map loaded once, by path
     std::string directory;           // the model file's directory (model.cpp:30)
     std::vector<std::string> texture_errors;   // maps that failed to load (model.cpp:221 prints them)
+    // the specular, normal and height maps, in a list of their own (the diffuse list and its
+    // indices stay what they were), each path loaded once; and the ones that failed
+    std::vector<Texture> shading_textures;
+    std::vector<std::string> shading_texture_errors;
 
     // Wavefront OBJ (+ mtllib).  Returns false and fills `err` on failure.  With
     // load_textures, each material's diffuse map is decoded from `directory` (PNG).
@@ -64,6 +76,9 @@ public:
     // `textures` is shared; a map that fails to decode is reported in texture_errors and
     // the material keeps Kd alone (the reference would sample an incomplete texture).
     void LoadTextures();
+    // the same for the three shading slots, into shading_textures (LoadObj calls it after
+    // LoadTextures when load_textures is set)
+    void LoadShadingTextures();
 
     // Apply a 4x4 column-major model matrix (r_voxelization.cpp:26-29 style):
     // p' = (m0 x + m4 y + m8 z + m12, ...), in that float order.

@@ -96,6 +96,41 @@ int vcth_texture(const vcth_model* m, uint32_t i, const uint8_t** rgba8, uint32_
     return 0;
 }
 
+int vcth_material_shininess(const vcth_model* m, uint32_t i, float* ns) {
+    if (!m || i >= m->m.materials.size()) return -1;
+    if (ns) *ns = m->m.materials[i].Ns;
+    return 0;
+}
+
+int vcth_material_shading_map(const vcth_model* m, uint32_t i, int slot, const char** path, int32_t* texture) {
+    if (!m || i >= m->m.materials.size() || slot < 0 || slot > 2) return -1;
+    const vcthost::Material& mt = m->m.materials[i];
+    if (path) *path = mt.shading_map[slot].c_str();
+    if (texture) *texture = mt.shadingMaps[slot];
+    return 0;
+}
+
+uint32_t vcth_num_shading_textures(const vcth_model* m) { return m ? (uint32_t)m->m.shading_textures.size() : 0u; }
+
+int vcth_shading_texture(const vcth_model* m, uint32_t i, const uint8_t** rgba8, uint32_t* width, uint32_t* height,
+                         const char** path) {
+    if (!m || i >= m->m.shading_textures.size()) return -1;
+    const vcthost::Texture& t = m->m.shading_textures[i];
+    if (rgba8) *rgba8 = t.rgba.data();
+    if (width) *width = t.width;
+    if (height) *height = t.height;
+    if (path) *path = t.path.c_str();
+    return 0;
+}
+
+uint32_t vcth_num_shading_texture_errors(const vcth_model* m) {
+    return m ? (uint32_t)m->m.shading_texture_errors.size() : 0u;
+}
+
+const char* vcth_shading_texture_error(const vcth_model* m, uint32_t i) {
+    return (m && i < m->m.shading_texture_errors.size()) ? m->m.shading_texture_errors[i].c_str() : nullptr;
+}
+
 uint32_t vcth_num_texture_errors(const vcth_model* m) { return m ? (uint32_t)m->m.texture_errors.size() : 0u; }
 
 const char* vcth_texture_error(const vcth_model* m, uint32_t i) {

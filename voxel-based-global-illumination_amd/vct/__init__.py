@@ -35,8 +35,9 @@ from ._lib import VctTemporalArgs, VctTemporalParams
 from ._lib import VctCone, VctConeQueryArgs, VctProbeGrid
 from ._lib import VctVoxelPickArgs, VctVoxelViewArgs
 from ._lib import VctEnvSky
+from ._lib import VctShadingDesc, VctShadingMaterial
 
-__all__ = ["VctEnvSky", "env_sky", "VctTemporalParams","Context", "VctError", "VctConfig", "VctCamera", "tiles_for_rank", "tile_offset", "VERTEX_FLOATS",
+__all__ = ["VctShadingMaterial","VctEnvSky", "env_sky", "VctTemporalParams","Context", "VctError", "VctConfig", "VctCamera", "tiles_for_rank", "tile_offset", "VERTEX_FLOATS",
            "VCT_ALL_RANKS", "comm_frame_layout", "VctLight", "directional_light", "point_light", "spot_light",
            "VctSky", "sky_light", "VctFog", "fog", "VctCone", "VctProbeGrid", "probe_grid", "VctMixedParams", "VctMixedHoles", "VCT_CONES_DIFFUSE", "VCT_CONES_SPECULAR"]
 
@@ -820,6 +821,61 @@ class Context:
         a.hit4 = self._dev(hit4, "hit4", _I32, 4 * n)
         a.cells = self._dev(cells, "cells", _I64, 1)
         self._check(fn(self.h, C.byref(cam), C.byref(a)), "voxel_view")
+
+    # -- the shading G-buffer (include/vct_shading.h) ------------------------
+    def set_shading(self, verts, idx=None, tri_material=None, materials=(), normal_offset=12, uv_offset=UV_OFFSET,
+                    tangent_offset=32, bitangent_offset=44):
+        """vct_set_shading: the attribute records and the material table of the current static
+        voxelization, from the host arrays that were voxelized (verts [V, F] float32, idx [3T]).
+        An offset of None marks the attribute absent; materials: VctShadingMaterial records or
+        vct.shading.ShadingMaterial.  set_shading(None) clears the set."""
+        fn = _lib.bind_shading_extension(self.lib, "vct_set_shading")
+        if verts is None:
+            self._check(fn(self.h, None), "set_shading")
+            return
+        verts = np.ascontiguousarray(verts, dtype=np.float32)
+        if verts.ndim != 2:
+            raise VctError(_EINVAL, f"set_shading: verts must be [V, F], got {verts.shape}")
+        idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+        mat = None if tri_material is None else np.ascontiguousarray(tri_material, dtype=np.uint32).reshape(-1)
+        if mat is not None and mat.size != idx.size // 3:
+            raise VctError(_EINVAL, f"set_shading: tri_material has {mat.size} entries for {idx.size // 3} triangles")
+        recs = [m.to_ctypes() if hasattr(m, "to_ctypes") else m for m in materials]
+        if not all(isinstance(m, VctShadingMaterial) for m in recs):
+            raise VctError(_EINVAL, "set_shading: materials must be VctShadingMaterial or ShadingMaterial records")
+        arr = (VctShadingMaterial * max(len(recs), 1))(*recs)
+        d = VctShadingDesc()
+        d.verts, d.vertex_stride, d.n_verts = verts.ctypes.data, verts.shape[1] * 4, verts.shape[0]
+        d.idx, d.n_idx = idx.ctypes.data, idx.size
+        d.tri_material = mat.ctypes.data if mat is not None else None
+        absent = lambda o: _lib.VCT_SHADING_NO_ATTR if o is None else int(o)
+        d.normal_offset, d.uv_offset = absent(normal_offset), absent(uv_offset)
+        d.tangent_offset, d.bitangent_offset = absent(tangent_offset), absent(bitangent_offset)
+        d.materials, d.n_materials = C.cast(arr, C.c_void_p), len(recs)
+        self._check(fn(self.h, C.byref(d)), "set_shading")
+
+    def gbuffer_shaded_device(self, cam, width, height, roughness, pos4, nrm4, alb4, ks4, geo4=None, tri_id=None,
+                              bary2=None):
+        """vct_gbuffer_shaded_device: the tile-binned pass with the shading normal in nrm4, the
+        material's roughness in alb4.w and Ks x map_Ks in ks4; optionally the geometric normal
+        (geo4, float32 [h, w, 4]), the triangle id (int32 [h, w]) and the barycentrics (float32
+        [h, w, 2])."""
+        fn = _lib.bind_shading_extension(self.lib, "vct_gbuffer_shaded_device")
+        c = cam.to_ctypes() if hasattr(cam, "to_ctypes") else cam
+        n = width * height
+        self._check(fn(self.h, C.byref(c), width, height, float(roughness),
+                       *self._gbuf_ptrs(width, height, pos4, nrm4, alb4), self._dev(ks4, "ks4", _F32, 4 * n),
+                       self._dev(geo4, "geo4", _F32, 4 * n), self._dev(tri_id, "tri_id", _I32, n),
+                       self._dev(bary2, "bary2", _F32, 2 * n)), "gbuffer_shaded")
+
+    def specular_tint_device(self, spec4, ks4, width, height, out4=None):
+        """vct_specular_tint_device: out.rgb = spec.rgb * ks.rgb, out.a = spec.a (in place when
+        out4 is None); call it before any composite."""
+        fn = _lib.bind_shading_extension(self.lib, "vct_specular_tint_device")
+        n = 4 * width * height
+        s = self._dev(spec4, "spec4", _F32, n)
+        self._check(fn(self.h, s, self._dev(ks4, "ks4", _F32, n), width, height,
+                       s if out4 is None else self._dev(out4, "out4", _F32, n)), "specular_tint")
 
     # -- volumetric fog (include/vct_fog.h) ----------------------------------
     def _fog(self, fog, what):

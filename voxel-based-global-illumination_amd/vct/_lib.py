@@ -93,6 +93,11 @@ ENV_EXTENSIONS = ("vct_set_env", "vct_env_size", "vct_env_download_level", "vct_
 VCT_ENV_MAX_DIM = 2048
 VCT_ENV_TEXEL_LIMIT = 2.0 ** 52
 
+# include/vct_shading.h: the shading G-buffer, likewise HIP only (bind_shading_extension)
+SHADING_EXTENSIONS = ("vct_set_shading", "vct_gbuffer_shaded_device", "vct_specular_tint_device")
+VCT_SHADING_NO_ATTR = 0xFFFFFFFF
+VCT_SHADING_FLIP_GREEN = 1
+
 STATUS = {0: "VCT_OK", 1: "VCT_EINVAL", 2: "VCT_ENOMEM", 3: "VCT_EDEVICE", 4: "VCT_ECOMM", 5: "VCT_ESTATE"}
 
 
@@ -295,6 +300,34 @@ class VctVoxelViewArgs(C.Structure):    # vct_voxel_view_args
         ("rgba8", C.c_void_p),
         ("hit4", C.c_void_p),
         ("cells", C.c_void_p),
+    ]
+
+
+class VctShadingMaterial(C.Structure):  # vct_shading_material, 32 bytes
+    _fields_ = [
+        ("ks", C.c_float * 3),
+        ("roughness", C.c_float),
+        ("normal_map", C.c_int32),
+        ("specular_map", C.c_int32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class VctShadingDesc(C.Structure):      # vct_shading_desc
+    _fields_ = [
+        ("verts", C.c_void_p),
+        ("vertex_stride", C.c_uint32),
+        ("n_verts", C.c_uint32),
+        ("idx", C.c_void_p),
+        ("n_idx", C.c_uint32),
+        ("tri_material", C.c_void_p),
+        ("normal_offset", C.c_uint32),
+        ("uv_offset", C.c_uint32),
+        ("tangent_offset", C.c_uint32),
+        ("bitangent_offset", C.c_uint32),
+        ("materials", C.c_void_p),
+        ("n_materials", C.c_uint32),
     ]
 
 
@@ -630,6 +663,26 @@ def bind_voxview_extension(lib: C.CDLL, name: str):
     except AttributeError:
         raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
                              "(include/vct_voxview.h is implemented by the HIP library only)") from None
+    fn.restype = res
+    fn.argtypes = args
+    return fn
+
+
+def bind_shading_extension(lib: C.CDLL, name: str):
+    """The include/vct_shading.h function `name` of `lib`, with its signature declared;
+    AttributeError (naming the library) if this implementation does not export it."""
+    P, u32, i32, f32 = C.c_void_p, C.c_uint32, C.c_int32, C.c_float
+    sig = {
+        "vct_set_shading": (i32, [P, C.POINTER(VctShadingDesc)]),
+        "vct_gbuffer_shaded_device": (i32, [P, C.POINTER(VctCamera), u32, u32, f32, P, P, P, P, P, P, P]),
+        "vct_specular_tint_device": (i32, [P, P, P, u32, u32, P]),
+    }
+    res, args = sig[name]
+    try:
+        fn = getattr(lib, name)
+    except AttributeError:
+        raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
+                             "(include/vct_shading.h is implemented by the HIP library only)") from None
     fn.restype = res
     fn.argtypes = args
     return fn
