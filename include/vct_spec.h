@@ -233,6 +233,11 @@
 #define VCT_VOXVIEW_SHADE_Y        1.0f
 #define VCT_VOXVIEW_SHADE_Z        0.6f
 #define VCT_VOXVIEW_STEPS_PER_CELL 3
+/* The HDR present ("present", below): the key of 2^-16 in the luminance meter, (127 - 16) << 4;
+ * the sRGB transfer's exponent, 1 / 2.4; and the largest exposure or key value, 2^64. */
+#define VCT_PRESENT_KEY0      1776u
+#define VCT_SRGB_INV_GAMMA    0.416666657f
+#define VCT_EXPOSURE_LIMIT    18446744073709551616.0f
 
 /* ---- light bounces (vct_inject_bounces, include/vct_bounce.h; no new literals) ------
  * L0 = the level-0 radiance at the call (K2's output), A / N = K1's resolved albedo and
@@ -936,4 +941,67 @@
  *  vct_specular_tint_device: out.rgb = spec.rgb * ks.rgb, out.a = spec.a; contents are data.
  *  No new literal. */
 
+/* ---- present (vct_luminance_meter_device / vct_exposure_update_device / vct_bloom_device /
+ * vct_present_device, include/vct_present.h; tests/present_ref.py restates it) ----------------
+ *  Each written operation rounds once; fmaf appears only where written.  A pixel p = (r, g, b, a)
+ *  of the linear frame is a BACKGROUND pixel when a == 0 (also -0.0f).
+ *    Y(p) = fmaf(0.0722f, b, fmaf(0.7152f, g, 0.2126f * r))
+ *  Meter.  A background pixel is counted nowhere.  A Y that is NaN, +-Inf or has its sign bit set
+ *    (also -0.0f) is `rejected`.  Otherwise key = bits(Y) >> 19,
+ *      bin = clamp(key - VCT_PRESENT_KEY0, 0, VCT_PRESENT_BINS - 1),  hist[bin] += 1, counted += 1,
+ *    under += 1 where key < VCT_PRESENT_KEY0, over += 1 where key - VCT_PRESENT_KEY0 >
+ *    VCT_PRESENT_BINS - 1.  Integer sums: exact, whatever the order.
+ *  Exposure update, 64-bit unsigned integers (the division truncates):
+ *    counted = counts[0];  lo = counted * low_permille / 1000;  hi = counted * high_permille / 1000
+ *    for b = 0 .. 511:       t = min(hist[b], lo);  keep[b] = hist[b] - t;  lo -= t
+ *    for b = 511 .. 0:       t = min(keep[b], hi);  keep[b] -= t;           hi -= t
+ *    n = sum keep[b];   S = sum b * keep[b];   M = (S * 256) / n          (n > 0)
+ *    mean = float_from_bits((VCT_PRESENT_KEY0 << 19) + (M << 11) + (1 << 18))
+ *    target = key_value / mean;  target = target < min_exposure ? min_exposure : (target >
+ *      max_exposure ? max_exposure : target)
+ *    prev = the previous record's exposure where a record is given and that value is finite and
+ *      > 0; otherwise there is no prev.
+ *    n == 0:                 exposure = target = prev, or 1.0f without one; mean = +0
+ *    no prev:                exposure = target
+ *    else: rate = target > prev ? rate_up : rate_down;
+ *          exposure = rate == 1.0f ? target : prev + (target - prev) * rate
+ *    out_state = {exposure, target, mean, (uint32_t)counted}
+ *  Bloom.  Level 0 is the frame (w_0 x h_0); level k is w_k = (w_{k-1} + 1) / 2 by h_k likewise;
+ *    the last level L is the first of params.levels and the level that is 1 x 1.  A tap (x, y) of
+ *    a level outside it is the tap at (min(x, w_k - 1), min(y, h_k - 1)) (and max(., 0)).
+ *    The contribution c(p) of a frame pixel, with E the exposure:
+ *      Ye = Y(p) * E;  wgt = Ye > 0 ? fmaxf(Ye - threshold, 0) / Ye : 0;  c = (r * wgt, g * wgt, b * wgt)
+ *      c = (+0, +0, +0) for a background pixel and where wgt or any channel of c is not finite.
+ *    box(t00, t10, t01, t11) = ((t00 + t10) + (t01 + t11)) * 0.25f per channel, t_ij the tap at
+ *      (2x + i, 2y + j) of the finer level.
+ *    D_1 = box of c over the frame;  D_k = box of D_{k-1}  (k = 2 .. L);  .w of every level is +0.
+ *    up2(P)(x, y), P of size pw x ph:  nx = x >> 1, fx = nx + ((x & 1) ? 1 : -1), ny and fy
+ *      likewise; with lerp(a, b) = fmaf(b - a, 0.25f, a):
+ *        up2 = lerp(lerp(P(nx, ny), P(fx, ny)), lerp(P(nx, fy), P(fx, fy)))
+ *      -- the 2x bilinear with weights 9, 3, 3, 1 over 16; a constant plane gives the constant.
+ *    U_L = D_L;  U_k = D_k + up2(U_{k+1})  (k = L - 1 .. 1).
+ *  Present.  E = the record's exposure when a record is given, else params.exposure.  Per channel
+ *    c of a pixel that is not a background pixel:
+ *      v = c * E;  with bloom: v = fmaf(up2(U_1)(x, y)_c, bloom_intensity, v)
+ *      v = v > 0 ? v : +0            (NaN, negatives and -0.0f)
+ *      d = 1.0f where v == +Inf, otherwise by the curve:
+ *        REINHARD         d = v / (1.0f + v)
+ *        REINHARD_WHITE   d = (v * (1.0f + v / (W * W))) / (1.0f + v);  d = d < 1.0f ? d : 1.0f
+ *        ACES             d = (v * fmaf(2.51f, v, 0.03f)) / fmaf(v, fmaf(2.43f, v, 0.59f), 0.14f);
+ *                         d = d < 1.0f ? d : 1.0f
+ *        CLAMP            d = v < 1.0f ? v : 1.0f
+ *      out_display4 = (d_r, d_g, d_b, a)
+ *      t = powf(d, VCT_INV_GAMMA)                                         (GAMMA22)
+ *      t = d <= 0.0031308f ? d * 12.92f : fmaf(1.055f, powf(d, VCT_SRGB_INV_GAMMA), -0.055f)   (SRGB)
+ *      byte = clamp(lroundf(t * 255.0f), 0, 255)                           (dither == 0: quant8)
+ *      byte = clamp((int)floorf(fmaf(t, 255.0f, (B[y & 3][x & 3] + 0.5f) / 16.0f)), 0, 255)
+ *        with B = {{0, 8, 2, 10}, {12, 4, 14, 6}, {3, 11, 1, 9}, {15, 7, 13, 5}}       (dither == 1)
+ *      out_rgba8 = r | g << 8 | b << 16 | 255 << 24
+ *    A background pixel: out_display4 = (VCT_CLEAR_R, VCT_CLEAR_G, VCT_CLEAR_B, a) and out_rgba8 =
+ *    lroundf(VCT_CLEAR_c * 255.0f) per channel, alpha 255: the composites' clear colour, outside
+ *    exposure, bloom, curve, transfer and dither.
+ *    With E = 1 from params, no bloom, REINHARD, GAMMA22 and no dither the bytes are the
+ *    composites' own (tone01 and quant8 of csrc/vct_view.h) for every finite radiance >= 0.
+ *  The section's literals (VCT_PRESENT_KEY0, VCT_SRGB_INV_GAMMA, VCT_EXPOSURE_LIMIT) stand with
+ *  VCT_INV_GAMMA, above. */
 #endif /* VCT_SPEC_H */

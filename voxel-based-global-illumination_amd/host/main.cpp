@@ -6,7 +6,8 @@
 //   vct_headless <model.obj> [grid=256] [width=800] [height=600] [frames=5] [out.ppm] [devices=1]
 //                [--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32]
 //                [--light SPEC]... [--shadow-tan T] [--sky Z[:H[:G]]] [--env FILE[:SCALE]] [--sky-view] [--mixed 2|4]
-//                [--fog DENSITY] [--temporal N] [--probes D] [--dynamic FILE.obj [--dynamic-offset x,y,z]]
+//                [--fog DENSITY] [--temporal N] [--probes D] [--present CURVE[:auto|:E][:bloom]]
+//                [--dynamic FILE.obj [--dynamic-offset x,y,z]]
 //                [--voxels LEVEL[:MODE]]...
 //   (devices > 1: one process drives that many GPUs through vct_create_multi)
 //   --model: the model matrix of the reference's draw, T(0,-1.75,0) S(0.2)
@@ -42,6 +43,11 @@
 //   --probes: D in 1 .. 256: a D^3 grid of ambient-cube probes (include/vct_query.h) over the grid's
 //            AABB, built after every relight; the composite reads the probe-sampled plane in place of
 //            K4's diffuse plane (the specular cone is still traced); absent: K4's diffuse plane;
+//   --present: CURVE[:auto|:E][:bloom], CURVE one of reinhard, white, aces, clamp: the frame is written
+//            through the HDR present (include/vct_present.h) of the composite's linear frame in place of
+//            the composite's own RGBA8 -- at the manual exposure E (default 1), or metered from the
+//            frame (auto), with five levels of bloom on request -- and as a PNG when the output path
+//            ends in .png; gamma 2.2, no dither.  `reinhard` alone gives the composite's bytes;
 //   --voxels: LEVEL[:MODE], repeatable: after the last frame, the voxel view (include/vct_voxview.h) of
 //            the frame's camera through pyramid level LEVEL is written next to the frame as
 //            <out stem>.voxels<LEVEL>-<MODE>.png, shaded by entry face.  MODE: radiance (default),
@@ -213,6 +219,49 @@ static bool parse_voxels(const std::string& spec, VoxelView* out) {
     return false;
 }
 
+// --present CURVE[:auto|:E][:bloom] (see above); false: malformed
+struct PresentSpec {
+    bool on = false, automatic = false, bloom = false;
+    uint32_t curve = VCT_CURVE_REINHARD;
+    float exposure = 1.0f;
+};
+static bool parse_present(const std::string& spec, PresentSpec* out) {
+    static const char* const names[4] = {"reinhard", "white", "aces", "clamp"};   // VCT_CURVE_* order
+    std::vector<std::string> tok;
+    for (size_t at = 0;;) {
+        const size_t colon = spec.find(':', at);
+        tok.push_back(spec.substr(at, colon == std::string::npos ? colon : colon - at));
+        if (colon == std::string::npos) break;
+        at = colon + 1;
+    }
+    PresentSpec p;
+    uint32_t c = 0;
+    while (c < 4 && tok[0] != names[c]) ++c;
+    if (c == 4 || tok.size() > 3) return false;
+    p.curve = c;
+    size_t i = 1;
+    if (i < tok.size() && tok[i] != "bloom") {
+        if (tok[i] == "auto") p.automatic = true;
+        else {
+            char* end = nullptr;
+            p.exposure = std::strtof(tok[i].c_str(), &end);
+            const char f = tok[i].empty() ? '\0' : tok[i][0];
+            if (!((f >= '0' && f <= '9') || f == '.') || *end || !(p.exposure > 0.0f) || !(p.exposure <= 18446744073709551616.0f))
+                return false;
+        }
+        ++i;
+    }
+    if (i < tok.size()) {
+        if (tok[i] != "bloom") return false;
+        p.bloom = true;
+        ++i;
+    }
+    if (i != tok.size()) return false;
+    p.on = true;
+    *out = p;
+    return true;
+}
+
 // one --dynamic-offset x,y,z -> out[3]; false: malformed (not exactly three finite numbers)
 static bool parse_offset(const std::string& spec, float out[3]) {
     const char* p = spec.c_str();
@@ -245,6 +294,7 @@ int main(int argc, char** argv) {
     float fog_density = 0.0f;
     uint32_t temporal = 0;
     uint32_t probes = 0;
+    PresentSpec present;
     std::vector<VoxelView> voxels;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -303,6 +353,13 @@ int main(int argc, char** argv) {
             }
             temporal = (uint32_t)t;
         }
+        else if (a == "--present" || a.rfind("--present=", 0) == 0) {
+            const std::string v = a == "--present" ? (i + 1 < argc ? argv[++i] : "") : a.substr(10);
+            if (!parse_present(v, &present)) {
+                std::fprintf(stderr, "malformed --present %s (reinhard|white|aces|clamp[:auto|:E][:bloom], 0 < E <= 2^64)\n", v.c_str());
+                return 2;
+            }
+        }
         else if (a == "--probes" || a.rfind("--probes=", 0) == 0) {
             const std::string v = a == "--probes" ? (i + 1 < argc ? argv[++i] : "") : a.substr(9);
             char* end = nullptr;
@@ -338,7 +395,7 @@ int main(int argc, char** argv) {
     if (sky_view && !has_sky && !has_env) { std::fprintf(stderr, "--sky-view needs --sky Z[:H[:G]] or --env FILE[:SCALE]\n"); return 2; }
     if (pos.empty()) {
         std::fprintf(stderr, "usage: %s model.obj [grid] [width] [height] [frames] [out.ppm] [devices] "
-                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] [--sky Z[:H[:G]]] [--env FILE[:SCALE]] [--sky-view] [--shaded] [--mixed 2|4] [--fog DENSITY] [--temporal N] [--probes D] [--voxels LEVEL[:MODE]]... "
+                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] [--sky Z[:H[:G]]] [--env FILE[:SCALE]] [--sky-view] [--shaded] [--mixed 2|4] [--fog DENSITY] [--temporal N] [--probes D] [--present CURVE[:auto|:E][:bloom]] [--voxels LEVEL[:MODE]]... "
                              "[--dynamic FILE.obj [--dynamic-offset x,y,z]] "
                              "[--light dir:d:rgb | point:p:rgb:range | spot:p:d:rgb:range:inner:outer]...\n",
                      argv[0]);
@@ -370,6 +427,11 @@ int main(int argc, char** argv) {
     s.fog_density = fog_density;
     s.temporal_len = temporal;
     s.probes = probes;
+    s.present = present.on;
+    s.present_curve = present.curve;
+    s.present_auto = present.automatic;
+    s.present_exposure = present.exposure;
+    s.present_bloom = present.bloom;
     if (ref_model) ReferenceModelMatrix(s.model);
 
     AssetsManager& A = AssetsManager::Instance();            // assets.cpp:22-45

@@ -375,17 +375,73 @@ vct_status ConeTraceRenderer::composite_terms(float* lin, uint32_t* rgba) {
                                 lin, rgba);
 }
 
+vct_status ConeTraceRenderer::present_frame(const float* lin, uint32_t* rgba) {
+    const uint32_t w = s_.width, h = s_.height;
+    // hist[512], counts[4] and the exposure record in one block; the bloom scratch in another
+    void *meter = nullptr, *scratch = nullptr;
+    vct_status st = vct_device_alloc(ctx_, 512 * 4 + 16 + 16, &meter);
+    uint32_t* hist = (uint32_t*)meter;
+    uint32_t* counts = hist + 512;
+    vct_exposure_state* state = s_.present_auto ? (vct_exposure_state*)(counts + 4) : nullptr;
+    if (st == VCT_OK && s_.present_auto) {
+        vct_exposure_params e{};
+        e.key_value = 0.18f; e.min_exposure = 1.0f / 4096.0f; e.max_exposure = 4096.0f;
+        e.low_permille = 100; e.high_permille = 20;
+        e.rate_up = e.rate_down = 1.0f;
+        st = vct_luminance_meter_device(ctx_, lin, w, h, hist, counts);
+        if (st == VCT_OK) st = vct_exposure_update_device(ctx_, hist, counts, &e, nullptr, state);
+    }
+    if (st == VCT_OK && s_.present_bloom) {
+        vct_bloom_params b{};
+        b.threshold = 1.0f; b.levels = 5; b.exposure = s_.present_exposure;
+        size_t bytes = 0;
+        st = vct_bloom_scratch_bytes(w, h, b.levels, &bytes);
+        if (st == VCT_OK) st = vct_device_alloc(ctx_, bytes, &scratch);
+        if (st == VCT_OK) st = vct_bloom_device(ctx_, lin, w, h, &b, state, (float*)scratch, bytes);
+    }
+    if (st == VCT_OK) {
+        vct_present_params p{};
+        p.curve = s_.present_curve; p.transfer = VCT_TRANSFER_GAMMA22; p.dither = 0;
+        p.exposure = s_.present_exposure; p.white = 4.0f; p.bloom_intensity = 0.25f;
+        st = vct_present_device(ctx_, lin, w, h, &p, state, (const float*)scratch, nullptr, rgba);
+    }
+    if (st == VCT_OK) st = vct_synchronize(ctx_);      // the blocks below are freed
+    if (scratch) vct_device_free(ctx_, scratch);
+    if (meter) vct_device_free(ctx_, meter);
+    return st;
+}
+
 bool ConeTraceRenderer::WritePPM(const std::string& path) {
     // row f3: composite + present on the device (include/vct.h vct_composite_device), then dump
     if (!ctx_) return false;
     const size_t px = (size_t)s_.width * s_.height;
-    void* rgba = nullptr;
+    void *rgba = nullptr, *lin = nullptr;
     if (!check(vct_device_alloc(ctx_, px * 4, &rgba), "alloc rgba8")) return false;
     std::vector<uint32_t> img(px);
-    const bool ok = check(composite(nullptr, (uint32_t*)rgba), "composite") &&
-                    check(vct_memcpy(ctx_, img.data(), rgba, px * 4, 1), "download rgba8");
+    bool ok;
+    if (s_.present)
+        ok = check(vct_device_alloc(ctx_, px * 16, &lin), "alloc linear frame") && check(composite((float*)lin, nullptr), "composite") &&
+             check(present_frame((const float*)lin, (uint32_t*)rgba), "present");
+    else
+        ok = check(composite(nullptr, (uint32_t*)rgba), "composite");
+    ok = ok && check(vct_memcpy(ctx_, img.data(), rgba, px * 4, 1), "download rgba8");
+    if (lin) vct_device_free(ctx_, lin);
     vct_device_free(ctx_, rgba);
     if (!ok) return false;
+    if (s_.present && path.size() > 4 && path.compare(path.size() - 4, 4, ".png") == 0) {
+        PngImage out;
+        out.width = s_.width; out.height = s_.height; out.comp = 3;
+        out.data.resize(px * 3);
+        for (size_t i = 0; i < px; ++i)
+            for (int k = 0; k < 3; ++k) out.data[3 * i + k] = (uint8_t)(img[i] >> (8 * k));
+        std::string err;
+        if (!WritePng(path, out, &err)) {
+            error_ = err;
+            std::fprintf(stderr, "present: %s\n", err.c_str());
+            return false;
+        }
+        return true;
+    }
     FILE* f = std::fopen(path.c_str(), "wb");
     if (!f) return false;
     std::fprintf(f, "P6\n%u %u\n255\n", s_.width, s_.height);

@@ -83,6 +83,16 @@ struct ConeTraceSettings {
     std::vector<float> env_texels;
     uint32_t env_size = 0;
     vct_env_sky env = {{{1.0f, 0.0f, 0.0f}, {0.0f, 0.0f, -1.0f}, {0.0f, 1.0f, 0.0f}}, 1.0f};
+    // the HDR present (include/vct_present.h): WritePPM takes the composite's linear frame through
+    // vct_present_device -- with present_auto the exposure is metered from the frame
+    // (vct_luminance_meter_device, vct_exposure_update_device: key 0.18, 100 / 20 permille trimmed,
+    // 2^-12 .. 2^12), with present_bloom five levels of vct_bloom_device (threshold 1, intensity
+    // 0.25) are added; gamma 2.2, no dither, W = 4 -- instead of the composite's own RGBA8
+    bool present = false;
+    uint32_t present_curve = 0;           // VCT_CURVE_*
+    bool present_auto = false;
+    float present_exposure = 1.0f;
+    bool present_bloom = false;
     // model matrix applied to the model's vertices before K1, column-major; main.cpp
     // sets the reference's T(0,-1.75,0) S(0.2) (r_voxelization.cpp:26-29) by default
     float model[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
@@ -108,6 +118,8 @@ public:
     double last_trace_ms() const { return last_ms_; }
     unsigned long long last_cone_steps() const { return last_steps_; }
     // composite + present (vct_composite_device: direct + albedo * indirect + specular) -> binary PPM
+    // With ConeTraceSettings::present the bytes are vct_present_device's, and a path ending in .png
+    // is written as a PNG (RGB)
     bool WritePPM(const std::string& path);
     // the same composite before tone mapping: width x height x 4 float32, row 0 = top, raw little-endian
     bool WriteLinear(const std::string& path);
@@ -122,6 +134,7 @@ private:
     bool relight();                       // inject -> mips (-> sky, bounces), as after every voxelization
     // row f3 into `lin` (float4) or `rgba` (packed 8-bit), with the light list when there is one
     vct_status composite(float* lin, uint32_t* rgba);
+    vct_status present_frame(const float* lin, uint32_t* rgba);  // the settings' present of a linear frame
     vct_status composite_surface(float* lin, uint32_t* rgba);   // the composite without the fog (with the sky behind it: sky_view)
     vct_status composite_terms(float* lin, uint32_t* rgba);     // direct + albedo * diffuse + specular by the frame's lights
     std::vector<vct_light> frame_lights() const;                // the light list, or the default light as one

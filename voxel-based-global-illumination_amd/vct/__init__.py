@@ -36,6 +36,7 @@ from ._lib import VctCone, VctConeQueryArgs, VctProbeGrid
 from ._lib import VctVoxelPickArgs, VctVoxelViewArgs
 from ._lib import VctEnvSky
 from ._lib import VctShadingDesc, VctShadingMaterial
+from ._lib import VctBloomParams, VctExposureParams, VctExposureState, VctPresentParams
 
 __all__ = ["VctShadingMaterial","VctEnvSky", "env_sky", "VctTemporalParams","Context", "VctError", "VctConfig", "VctCamera", "tiles_for_rank", "tile_offset", "VERTEX_FLOATS",
            "VCT_ALL_RANKS", "comm_frame_layout", "VctLight", "directional_light", "point_light", "spot_light",

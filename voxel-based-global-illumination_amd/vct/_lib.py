@@ -98,6 +98,15 @@ SHADING_EXTENSIONS = ("vct_set_shading", "vct_gbuffer_shaded_device", "vct_specu
 VCT_SHADING_NO_ATTR = 0xFFFFFFFF
 VCT_SHADING_FLIP_GREEN = 1
 
+# include/vct_present.h: the HDR present, likewise HIP only (bind_present_extension)
+PRESENT_EXTENSIONS = ("vct_luminance_meter_device", "vct_exposure_update_device", "vct_bloom_scratch_bytes",
+                      "vct_bloom_device", "vct_present_device")
+VCT_PRESENT_BINS, VCT_PRESENT_KEY0, VCT_PRESENT_MAX_DIM, VCT_BLOOM_MAX_LEVELS = 512, (127 - 16) << 4, 16384, 8
+VCT_CURVE_REINHARD, VCT_CURVE_REINHARD_WHITE, VCT_CURVE_ACES, VCT_CURVE_CLAMP = 0, 1, 2, 3
+VCT_CURVES = {"reinhard": 0, "white": 1, "aces": 2, "clamp": 3}
+VCT_TRANSFER_GAMMA22, VCT_TRANSFER_SRGB = 0, 1
+VCT_EXPOSURE_LIMIT = 2.0 ** 64
+
 STATUS = {0: "VCT_OK", 1: "VCT_EINVAL", 2: "VCT_ENOMEM", 3: "VCT_EDEVICE", 4: "VCT_ECOMM", 5: "VCT_ESTATE"}
 
 
@@ -328,6 +337,49 @@ class VctShadingDesc(C.Structure):      # vct_shading_desc
         ("bitangent_offset", C.c_uint32),
         ("materials", C.c_void_p),
         ("n_materials", C.c_uint32),
+    ]
+
+
+class VctExposureState(C.Structure):   # vct_exposure_state, 16 bytes (a device record)
+    _fields_ = [
+        ("exposure", C.c_float),
+        ("target", C.c_float),
+        ("mean_luminance", C.c_float),
+        ("counted", C.c_uint32),
+    ]
+
+
+class VctExposureParams(C.Structure):  # vct_exposure_params, 32 bytes
+    _fields_ = [
+        ("key_value", C.c_float),
+        ("min_exposure", C.c_float),
+        ("max_exposure", C.c_float),
+        ("low_permille", C.c_uint32),
+        ("high_permille", C.c_uint32),
+        ("rate_up", C.c_float),
+        ("rate_down", C.c_float),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class VctBloomParams(C.Structure):     # vct_bloom_params, 16 bytes
+    _fields_ = [
+        ("threshold", C.c_float),
+        ("levels", C.c_uint32),
+        ("exposure", C.c_float),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class VctPresentParams(C.Structure):   # vct_present_params, 32 bytes
+    _fields_ = [
+        ("curve", C.c_uint32),
+        ("transfer", C.c_uint32),
+        ("dither", C.c_uint32),
+        ("exposure", C.c_float),
+        ("white", C.c_float),
+        ("bloom_intensity", C.c_float),
+        ("reserved", C.c_uint32 * 2),
     ]
 
 
@@ -686,6 +738,38 @@ def bind_shading_extension(lib: C.CDLL, name: str):
     fn.restype = res
     fn.argtypes = args
     return fn
+
+
+def bind_present_extension(lib: C.CDLL, name: str):
+    """The include/vct_present.h function `name` of `lib`, with its signature declared;
+    AttributeError (naming the library) if this implementation does not export it."""
+    P, u32, i32 = C.c_void_p, C.c_uint32, C.c_int32
+    sig = {
+        "vct_luminance_meter_device": (i32, [P, P, u32, u32, P, P]),
+        "vct_exposure_update_device": (i32, [P, P, P, C.POINTER(VctExposureParams), P, P]),
+        "vct_bloom_scratch_bytes": (i32, [u32, u32, u32, C.POINTER(C.c_size_t)]),
+        "vct_bloom_device": (i32, [P, P, u32, u32, C.POINTER(VctBloomParams), P, P, C.c_size_t]),
+        "vct_present_device": (i32, [P, P, u32, u32, C.POINTER(VctPresentParams), P, P, P, P]),
+    }
+    res, args = sig[name]
+    try:
+        fn = getattr(lib, name)
+    except AttributeError:
+        raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
+                             "(include/vct_present.h is implemented by the HIP library only)") from None
+    fn.restype = res
+    fn.argtypes = args
+    return fn
+
+
+def debug_present(lib: C.CDLL, agg: int = -1) -> int:
+    """Tool hook (vct_debug_present, not part of the headers).  agg >= 0, process-wide: 0 (the
+    default) makes the luminance meter send one LDS atomic per lane, 1 folds the lanes that share
+    the wave's first live key into one add.  -> the form in force."""
+    fn = lib.vct_debug_present
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int]
+    return int(fn(int(agg)))
 
 
 def bind_dynamic_extension(lib: C.CDLL, name: str):
