@@ -1,7 +1,8 @@
 // vct_alpha_march.h — the alpha-only cone march that vct_shadow.hip (one cone per light and
-// pixel) and vct_sky.hip (the diffuse cone set per receiver) share: the step rows a wave
-// holds, the alpha sample of one level with its two address paths, the lockstep march of
-// vct_spec.h "shadow cones" steps 1-5, and the context's set of step tables.
+// pixel) and vct_sky_march.h (the diffuse cone set per receiver, the specular cone per pixel)
+// share: the step rows a wave holds, the alpha sample of one level with its two address
+// paths, the lockstep march of vct_spec.h "shadow cones" steps 1-5 (cone<>), the same march
+// with an aperture per lane (cone_lane<>), and the context's set of step tables.
 //
 // The device code is templated on the kernel's argument record K, which must have
 //     AlphaRange lvl[kMaxLevels + 1];  int n, L, lgn, aniso;  float tmax;
@@ -166,6 +167,70 @@ __device__ __forceinline__ float cone(const K& k, const StepRow* __restrict__ ta
         const float oma = 1.0f - a;
         a = act ? fmaf(oma, s, a) : a;
         steps += act ? 1u : 0u;
+    }
+    return a;
+}
+
+// one alpha cone per lane, each lane with an aperture tau of its own ("shadow cones" 1-5 with
+// t_lim = +inf); returns a.  No step table applies: every lane derives its steps in registers
+// (t, D = max(1, 2 tau t), m = log2 D, l0, fr: K4's per-lane march).  sample_alpha wants a
+// wave-uniform level, so a step loops over the levels present among the lanes that still
+// march: the first pending lane's l0 is read onto the scalar unit, the lanes of that level
+// sample and leave the pending mask.  A wave whose lanes share one tau has one t sequence and
+// runs the loop once per step (the lockstep march, with no special case); a wave of mixed tau
+// pays one pass per distinct level.  The second level of a step (fr > 0, l0 < L) is handled
+// the same way.  Addresses: a lane outside the pass is an ended lane to sample_alpha, so its
+// loads go past the buffer range (O32) or read texel 0 and select zero (64-bit); a lane inside
+// it has a finite p in [0, n]^3 and 0 <= l <= L, the range sample_alpha's corners are checked
+// against.  tau must be clamped to VCT_SPEC_TAU_MIN..MAX by the caller.
+template <bool O32, class K>
+__device__ __forceinline__ float cone_lane(const K& k, bool need, float ox, float oy, float oz, float dx, float dy,
+                                           float dz, float tau, uint32_t& steps) {
+    const float tau2 = 2.0f * tau;
+    const float nf = (float)k.n, Lf = (float)k.L;
+    const int fx = dx >= 0.0f ? VCT_FACE_PX : VCT_FACE_NX;
+    const int fy = dy >= 0.0f ? VCT_FACE_PY : VCT_FACE_NY;
+    const int fz = dz >= 0.0f ? VCT_FACE_PZ : VCT_FACE_NZ;
+    const float wdx = dx * dx, wdy = dy * dy, wdz = dz * dz;
+    float a = 0.0f, t = 1.0f;
+    bool act = need;
+    for (;;) {
+        // step 1; t grows by at least 0.5 a step, so the loop ends
+        const float px = ox + dx * t, py = oy + dy * t, pz = oz + dz * t;
+        act = act & (a < VCT_ALPHA_STOP) & (t <= k.tmax) &
+              ((px >= 0.0f) & (px <= nf) & (py >= 0.0f) & (py <= nf) & (pz >= 0.0f) & (pz <= nf));
+        const unsigned long long am = __builtin_amdgcn_ballot_w64(act);
+        if (am == 0ull) break;
+        // step 2, per lane (tau is clamped and t <= tmax on a marching lane: 0 <= m <= L)
+        const float D = fmaxf(1.0f, tau2 * t);
+        const float m = fminf(spec_log2(D), Lf);
+        const int l0 = act ? (int)m : 0;
+        const float fr = m - (float)l0;
+        // step 3: one pass per level present among the marching lanes
+        float s = 0.0f;
+        for (unsigned long long pend = am; pend != 0ull;) {
+            const int l = __builtin_amdgcn_readlane(l0, __builtin_ctzll(pend));
+            const bool mine = act & (l0 == l);
+            const float v = sample_alpha<O32>(k, l, mine, px, py, pz, fx, fy, fz, wdx, wdy, wdz);
+            s = mine ? v : s;
+            pend &= ~__builtin_amdgcn_ballot_w64(mine);
+        }
+        // step 4: the same over the lanes that blend in level l0 + 1
+        const bool two = act & (fr > 0.0f) & (l0 < k.L);
+        float s1 = 0.0f;
+        for (unsigned long long pend = __builtin_amdgcn_ballot_w64(two); pend != 0ull;) {
+            const int l = __builtin_amdgcn_readlane(l0, __builtin_ctzll(pend));
+            const bool mine = two & (l0 == l);
+            const float v = sample_alpha<O32>(k, l + 1, mine, px, py, pz, fx, fy, fz, wdx, wdy, wdz);
+            s1 = mine ? v : s1;
+            pend &= ~__builtin_amdgcn_ballot_w64(mine);
+        }
+        s = two ? fmaf(fr, s1, (1.0f - fr) * s) : s;
+        // step 5
+        const float oma = 1.0f - a;
+        a = act ? fmaf(oma, s, a) : a;
+        steps += act ? 1u : 0u;
+        t = t + VCT_STEP_SCALE * D;
     }
     return a;
 }

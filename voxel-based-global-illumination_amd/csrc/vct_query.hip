@@ -4,7 +4,7 @@
 //   kquery        one cone per lane, in list order: an arbitrary (origin, direction, aperture,
 //                 limit) record marched through the RGBA pyramid by K4's rule.  Every lane has
 //                 its own aperture, so it derives its own (t, D, l0, fr) in registers with the
-//                 spec's log2, as ksky_spec (vct_sky_view.hip) does; no step table applies.
+//                 spec's log2, as cone_lane (vct_alpha_march.h) does; no step table applies.
 //                 A step loops over the levels present among the lanes that still march: the
 //                 first pending lane's level is read onto the scalar unit (so the level's base
 //                 and shifts stay scalar), the lanes of that level sample under their own exec
