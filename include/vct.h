@@ -348,7 +348,10 @@ vct_status vct_gbuffer_raster_device(vct_ctx* ctx, const vct_camera* cam, uint32
  * out_linear4 (float4, a = 1 / 0 background) and/or out_rgba8 (Reinhard, gamma
  * 1/2.2; background = the reference's clear colour, r_voxelization.cpp:8).
  * Device pointers: the G-buffer of the frame and vct_trace_device's outputs.
- * Either output may be NULL, not both.  Needs vct_voxelize. */
+ * Either output may be NULL, not both.  Needs vct_voxelize.
+ * Any pixel with pos4.w != 0 is legal, whatever its position and normal hold: the shadow walk
+ * starts only from a cone origin q with 0 <= q < n on every axis in float32, and the shadow is
+ * 1 otherwise, for a NaN too (vct_spec.h "shadow-walk receiver rule"). */
 vct_status vct_composite_device(vct_ctx* ctx, const float* pos4, const float* nrm4, const float* alb4,
                                 const float* diffuse4, const float* spec4, uint32_t width, uint32_t height,
                                 const float dir_to_light[3], const float color[3], float* out_linear4,

@@ -92,7 +92,8 @@ vct_status vct_inject_emission(vct_ctx* ctx, float scale);
  * the hard voxel walk, as in vct_composite_lights_device; with an empty emission grid or
  * scale = +0 the output then equals that function's bit for bit.  scale as for
  * vct_inject_emission; every other precondition and output is
- * vct_composite_shadowed_device's. */
+ * vct_composite_shadowed_device's.  The hard walks of vis = NULL start by the "shadow-walk
+ * receiver rule" of vct_spec.h, as vct_composite_lights_device's do. */
 vct_status vct_composite_emissive_device(vct_ctx* ctx, const float* pos4, const float* nrm4, const float* alb4,
                                          const float* diffuse4, const float* spec4,
                                          uint32_t width, uint32_t height,

@@ -60,8 +60,10 @@ typedef struct vct_light {      /* 60 bytes, host memory */
 vct_status vct_inject_lights(vct_ctx* ctx, const vct_light* lights, uint32_t n_lights);
 
 /* vct_composite_device with the direct term summed over `lights` (n_lights = 0: no direct
- * term).  Every other precondition and output is vct_composite_device's; the lights are
- * validated as by vct_inject_lights. */
+ * term).  Every other precondition and output is vct_composite_device's, the start of a
+ * pixel's shadow walks included (vct_spec.h "shadow-walk receiver rule": V = 1 for a pixel
+ * whose cone origin is NaN or outside the grid); the lights are validated as by
+ * vct_inject_lights. */
 vct_status vct_composite_lights_device(vct_ctx* ctx, const float* pos4, const float* nrm4, const float* alb4,
                                        const float* diffuse4, const float* spec4, uint32_t width, uint32_t height,
                                        const vct_light* lights, uint32_t n_lights,

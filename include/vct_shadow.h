@@ -34,6 +34,9 @@ extern "C" {
  * > 0: a shadow cone of that half-angle tangent, clamped to [VCT_SPEC_TAU_MIN, VCT_SPEC_TAU_MAX].
  * vis[j][y][x] is +0 for a background pixel and for a light the pixel skips (facing away,
  * out of range, outside the spot cone).
+ * A pixel whose cone origin has a NaN component, or lies far outside the grid, is legal: a hard
+ * light gives it V = 1 without a walk (vct_spec.h "shadow-walk receiver rule"), a soft light
+ * V = 1 with no cone step, so the two agree.
  * cone_steps: device counter (8-byte aligned), += the cone steps of this call, or NULL.
  * The context keeps one small step table per distinct clamped aperture it has met, built on
  * the device by the first call that uses it.  The tables belong to the context, not to a

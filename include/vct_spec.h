@@ -140,6 +140,32 @@
  *    contribution is below 2^15 * 2^105 * 2 = 2^121 and the sum below 2^127 < FLT_MAX:
  *    VCT_COLOR_LIMIT = 2^127 / (VCT_KD_LIMIT * 2 * VCT_MAX_LIGHTS) = 2^105. */
 #define VCT_COLOR_LIMIT     4.05648192e31f   /* 2^105 exactly */
+
+/* Shadow-walk receiver rule (what a caller's pixel means to the A.3 shadow walk: the composites
+ * vct_composite_device, vct_composite_lights_device, vct_composite_emissive_device with vis NULL,
+ * and the hard lights, tan_half 0, of vct_shadow_cones_device; every implementation restates it):
+ *  A pixel is legal whenever pos4.w != 0; its q_a = (P_a - g0_a) * inv_h + N_a may be anything a
+ *  float32 holds.  The walk from a receiver starts only if
+ *      0 <= q_a && q_a < (float)n      in float32, for a = x, y, z.
+ *  The compare happens BEFORE any float -> int conversion.  A NaN fails it; -0.0f passes (and
+ *  floorf(-0.0f) converts to cell 0).  Otherwise V = 1 and nothing is read: the receiver lies
+ *  outside the grid, which no voxel shadows.
+ *  Equivalence: for every q_a an int holds (-2^31 <= q_a < 2^31), floorf(q_a) < 0 exactly when
+ *  q_a < 0 and floorf(q_a) >= n exactly when q_a >= n (n is an integer), so the test equals
+ *  A.3's own "start cell outside the grid gives V = 1" on v_a = (int)floorf(q_a) bit for bit:
+ *  no result that was defined changes.  What the rule adds is a result for the q no int
+ *  holds -- NaN, +-inf, |q_a| >= 2^31 -- where (int)floorf(q_a) is undefined in C and differs
+ *  between machines (x86 gives INT_MIN for all of them; gfx950 saturates and turns NaN into 0, a
+ *  start cell inside the grid, with a tm_a of NaN that loses every <=, so that an axis the walk
+ *  needs can never move).
+ *  A soft light (tan_half != 0) keeps what "shadow cones" gives: for a receiver with a NaN
+ *  component, or one too far out for t <= t_max to bring p back (+-inf, 1e30, 2^31), step 1
+ *  ends the cone before its first sample (a NaN fails the compares of "p outside [0, n]^3"):
+ *  0 steps, a = +0, V = 1.  The hard and the soft path of one call therefore agree on every
+ *  such receiver.  (A receiver just outside the grid whose cone re-enters it marches, as
+ *  before; its hard walk gives 1, as before.)
+ *  K2's receivers (an occupied voxel's centre plus its K1 normal) are finite and inside the
+ *  test's int range by the K1 input rule; K2 keeps A.3's test on the converted cell. */
 /* "environment sky" (below): the largest texel of a map and the largest scale of a record, so
  * that Env <= 2^104 (1 + 2^-21) stays below VCT_COLOR_LIMIT */
 #define VCT_ENV_TEXEL_LIMIT 4503599627370496.0f  /* 2^52 exactly */
@@ -296,7 +322,8 @@
  *  for cell, with one more end.  t_e is the t at which the current cell was entered: 0 for
  *  the first cell; after a step, the tm value that was the minimum chosen (before td is
  *  added to it).  Before a cell is tested: t_e >= t_lim gives V = 1 (the light is
- *  reached).  A start cell outside the grid gives V = 1 as in A.3.
+ *  reached).  A start cell outside the grid gives V = 1 as in A.3; for the composite's receiver
+ *  that test is the "shadow-walk receiver rule" (float compares on q, before the conversion).
  *  Sum:  contrib_c = (((A_c * color_c) * ndl) * f) * V
  *        acc = +0;  acc_c = acc_c + contrib_c  for the lights not skipped, in list order
  *    K2 writes (acc, 1) at the voxel; the composite uses direct = acc in

@@ -643,6 +643,7 @@ vct_status vct_composite_device(vct_ctx* c, const float* pos4, const float* nrm4
     if (!c->voxelized) return fail(c, VCT_ESTATE, "composite before voxelize");
     const char* bad = bad_light(dir_to_light, color);   /* K2 input rule, as vct_inject_directional */
     if (bad) return fail(c, VCT_EINVAL, bad);
+    /* no entry test of its own: the shadow-walk receiver rule (vct_spec.h) is vo_composite's */
     vo_composite(c->n, c->cfg.aabb_min, c->cfg.extent, c->albedo_occ, pos4, nrm4, alb4, diffuse4, spec4, w, h,
                  dir_to_light, color, out_linear4, out_rgba8);
     return VCT_OK;

@@ -307,6 +307,17 @@ static float dda_visibility(const float* albedo_occ4, uint32_t n, v3 q, v3 l) {
     }
 }
 
+/* Shadow-walk receiver rule (vct_spec.h): a walk from a caller's receiver (a G-buffer pixel)
+ * starts only if 0 <= q_a < n holds in float32 on every axis, tested before any conversion;
+ * otherwise V = 1 and nothing is read.  A NaN fails the compares, -0.0f passes.  For every q
+ * an int holds this is dda_visibility's own floor(q) test; for the rest it replaces an
+ * undefined (int)floorf(q).  K2's receivers (vo_inject: a voxel centre plus a K1 normal) are
+ * finite and in range by K1's rule and go straight to the walk. */
+static int walk_starts(uint32_t n, v3 q) {
+    const float fn = (float)n;
+    return q.x >= 0.0f && q.x < fn && q.y >= 0.0f && q.y < fn && q.z >= 0.0f && q.z < fn;
+}
+
 void vo_inject(uint32_t n, const float* albedo_occ4, const float* normal4,
                const float dir_to_light[3], const float color[3], float* r0) {
     v3 l = {dir_to_light[0], dir_to_light[1], dir_to_light[2]};
@@ -368,7 +379,7 @@ void vo_composite(uint32_t n, const float g0[3], float extent, const float* albe
         float d[3] = {0.0f, 0.0f, 0.0f};
         if (ndl > 0.0f) {
             v3 q = {(P[0] - g0[0]) * inv_h + nm.x, (P[1] - g0[1]) * inv_h + nm.y, (P[2] - g0[2]) * inv_h + nm.z};
-            float vis = dda_visibility(albedo_occ4, n, q, l);
+            float vis = walk_starts(n, q) ? dda_visibility(albedo_occ4, n, q, l) : 1.0f;
             for (int c = 0; c < 3; ++c) d[c] = ((A[c] * color[c]) * ndl) * vis;
         }
         float f[3];

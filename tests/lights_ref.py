@@ -83,17 +83,27 @@ def evaluate(L, q, N):
     return l, f, ndl, t_lim, {"zero": zero, "culled": culled, "back": back, "walk": walk}
 
 
-def walk(occ, q, l, t_lim):
+def walk_starts(q, n):
+    """The shadow-walk receiver rule (vct_spec.h): 0 <= q_a < n in float32 on every axis (a
+    NaN fails, -0.0 passes), tested before any conversion.  q: [R, 3] float32 -> [R] bool."""
+    q = np.asarray(q, F)
+    with np.errstate(all="ignore"):
+        return np.all((q >= F(0.0)) & (q < F(n)), axis=1)
+
+
+def walk(occ, q, l, t_lim, cells=None):
     """A.3 with the t_e >= t_lim end, all receivers in lockstep.  occ: [n, n, n] bool
     (z, y, x).  -> V [R] float32 and the end of every walk: 0 blocked, 1 left the grid
-    (or started outside it), 2 reached the light."""
+    (or started outside it), 2 reached the light.  A walk starts by the receiver rule
+    (`walk_starts`); only a q that passes it is converted to a cell.  cells (an int64 [R]
+    array) receives the cells every walk tests."""
     n = occ.shape[0]
     R = q.shape[0]
     V = np.zeros(R, F)
     end = np.zeros(R, np.int8)
     with np.errstate(all="ignore"):
-        v = np.floor(q).astype(np.int64)
-        outside = np.any((v < 0) | (v >= n), axis=1)
+        outside = ~walk_starts(q, n)
+        v = np.floor(np.where(outside[:, None], F(0.0), q)).astype(np.int64)
         V[outside] = 1.0
         end[outside] = 1
         s = np.where(l > 0, 1, np.where(l < 0, -1, 0)).astype(np.int64)
@@ -108,6 +118,8 @@ def walk(occ, q, l, t_lim):
     v, s, td, tm, t_e, t_lim = v[act], s[act], td[act], tm[act], t_e[act], t_lim[act]
     while act.size:
         reached = t_e >= t_lim
+        if cells is not None:
+            cells[act[~reached]] += 1
         hit = ~reached & occ[v[:, 2], v[:, 1], v[:, 0]]
         V[act[reached]] = 1.0
         end[act[reached]] = 2
@@ -183,7 +195,8 @@ def composite(n, g0, E, albedo_occ, pos4, nrm4, alb4, diffuse4, spec4, lights, s
     fy, fx = np.nonzero(pos4[..., 3] != 0)
     P, N, A = pos4[fy, fx, :3], nrm4[fy, fx, :3], alb4[fy, fx, :3]
     inv_h = F(n) / F(E)
-    q = (P - _f3(g0)[None, :]) * inv_h + N
+    with np.errstate(all="ignore"):                  # a pixel's position and normal may hold anything
+        q = (P - _f3(g0)[None, :]) * inv_h + N
     direct = _direct(occ, q, N, A, lights, n, g0, E, stats)
     out[fy, fx, :3] = (direct + A * D[fy, fx, :3]) + S[fy, fx, :3]
     out[fy, fx, 3] = 1.0

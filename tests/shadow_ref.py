@@ -8,7 +8,8 @@ numpy operation in the order the spec gives.  The spec's fused operations go thr
 :func:`fmaf`, an exact vectorised binary32 fma.
 
 The per-light terms, the skip rule and the hard walk are tests/lights_ref.py's (the walk under
-the K2 input rule of vct_spec.h: an axis whose td is not finite does not move).
+the K2 input rule of vct_spec.h: an axis whose td is not finite does not move; its start under
+the shadow-walk receiver rule: V = 1 without a walk unless 0 <= q < n in float32).
 """
 from __future__ import annotations
 
@@ -159,7 +160,8 @@ def shadow(n, g0, E, albedo_occ, alpha, aniso, pos4, nrm4, lights, tan_half):
     fy, fx = np.nonzero(pos4[..., 3] != 0)
     P, N = pos4[fy, fx, :3], nrm4[fy, fx, :3]
     inv_h = F(n) / F(E)
-    q = (P - _f3(g0)[None, :]) * inv_h + N
+    with np.errstate(all="ignore"):                  # a pixel's position and normal may hold anything
+        q = (P - _f3(g0)[None, :]) * inv_h + N
     total, pairs = 0, []
     for j, light in enumerate(lights):
         Lc = lights_ref.prepare(light, n, g0, E)
@@ -187,7 +189,8 @@ def composite(n, g0, E, pos4, nrm4, alb4, diffuse4, spec4, lights, vis):
     fy, fx = np.nonzero(pos4[..., 3] != 0)
     P, N, A = pos4[fy, fx, :3], nrm4[fy, fx, :3], alb4[fy, fx, :3]
     inv_h = F(n) / F(E)
-    q = (P - _f3(g0)[None, :]) * inv_h + N
+    with np.errstate(all="ignore"):                  # a pixel's position and normal may hold anything
+        q = (P - _f3(g0)[None, :]) * inv_h + N
     acc = np.zeros((q.shape[0], 3), F)
     for j, light in enumerate(lights):
         Lc = lights_ref.prepare(light, n, g0, E)

@@ -294,13 +294,17 @@ def test_composite(gpu_ready, oracle_mod):
 
 def test_composite_small_and_hostile_frames(gpu_ready, oracle_mod):
     """A 1 x 1 frame, an all-background frame, and a G-buffer whose positions are outside the
-    grid, on its faces, or NaN / Inf (Em = +0 there).  Point and spot lights only: a receiver with a
-    non-finite q skips them (r2 > 0 fails), so every output stays a defined number."""
+    grid, on its faces, or NaN / Inf (Em = +0 there).  Light set S with its directional light, and
+    a second directional light that the frame's normal (0, -1, 0) faces: a receiver with a NaN q
+    skips the point and spot lights (r2 > 0 fails), and its hard walk toward a directional light
+    gives V = 1 by the shadow-walk receiver rule of vct_spec.h, so every output is a defined number."""
     import torch
     n = 32
     L = R.lamp(n)
     g = L["grid"]
-    lights = [l for l in lights_ref.light_set_s(n) if l.type != 0]
+    import vct
+    lights = lights_ref.light_set_s(n) + [vct.directional_light((0.3, -1.0, 0.2), (0.5, 0.25, 0.75))]
+    assert sum(l.type == 0 for l in lights) == 2
     ctx = _lamp_ctx(n)
     z, y, x = (a[0] for a in np.nonzero(L["em"]["emissive"]))
     hh = F(L["E"]) / F(n)
@@ -323,6 +327,9 @@ def test_composite_small_and_hostile_frames(gpu_ready, oracle_mod):
         Em, hit = R.lookup(n, L["g0"], L["E"], L["em"]["E"], pos)
         base = lights_ref.composite(n, L["g0"], L["E"], g["albedo_occ"], pos, nrm, alb, Dn, Sn, lights)
         assert np.isfinite(base).all()
+        if len(sel) == 10:        # the second directional light reaches the non-finite rows with V = 1
+            lit = lights_ref.composite(n, L["g0"], L["E"], g["albedo_occ"], pos, nrm, alb, Dn, Sn, lights[:-1])
+            assert (base[1, 0:4, :3] > lit[1, 0:4, :3]).all()      # rows 5..8: NaN x, +inf y, -inf z, 1e30
         assert bits_equal(lin, R.composite(base, pos, Em, 1.5)), (w, h, sel)
         assert hit.reshape(-1).tolist() == [k == 0 for k in sel]
         bg = pos[..., 3] == 0

@@ -7,12 +7,15 @@ Every comparison takes the GPU's own level 0 and pyramid (as test_trace_parity d
 are n = 16 and n = 32 and frames 64 x 48.  One catalogue family per test, so a difference
 names its family; the message names the first differing pixels and their entries.
 
-The other consumers of the frame (test_consumer_*) run every entry for which their reference
-defines a result.  Left out there, and why: pos_big+ and pos_big- (1e30) and the whole
-non-finite family.  The references' shadow walks start with a float -> int conversion of the
-cone origin ((int)floorf(q) in vo_composite, floor(q).astype(int64) in lights_ref.walk),
-which is undefined for a value no integer holds and for NaN.  Every other entry (the 1e3 E
-positions are about 1.6e4 voxels out and fit an int) is compared.
+The other consumers of the frame (test_consumer_*) run every entry, pos_big+ and pos_big-
+(1e30) and the whole non-finite family included: under the "shadow-walk receiver rule" of
+include/vct_spec.h a walk starts only from a cone origin with 0 <= q < n in float32, tested
+before any float -> int conversion, and V = 1 otherwise, so every reference defines every
+pixel (tests/test_receiver_inputs.py, tests/test_receiver_inputs_gpu.py have the rule's own
+catalogue).  One entry leaves the finite numbers: n_posinf_y faces the directional light with
+n.l = +inf, so its direct term and its linear colour are +inf, in the references and on the
+device alike; its RGBA8 is not compared (the tone curve of +inf is NaN, whose rounding to an
+integer no reference defines).
 
 On these grids g0 != 0, so pos_denorm's x offset is absorbed by g0 (its y is a
 true denormal); the CPU comparison in test_trace_inputs.py uses g0 = 0."""
@@ -399,14 +402,15 @@ def test_tables_path_counters(gpu_ready, oracle_mod, steps, table):
 # ---------------------------------------------------------------------------
 # E  the other consumers of the hostile frame
 # ---------------------------------------------------------------------------
-E_FAMILIES = ("position", "posw", "normal", "roughness")
-E_EXCLUDE = ("pos_big+", "pos_big-")        # see the module docstring
+E_FAMILIES = TI.FAMILIES
+E_EXCLUDE = ()                              # nothing is left out: see the module docstring
+INF_COLOUR = ("n_posinf_y",)                # n.l = +inf under the directional light
 
 
 def _consumer_setup(n=16):
     """cornell at n on the GPU with light set S injected (lights_ref.cornell's scene and grid),
-    the hostile frame without the entries the references do not define, random finite
-    diffuse / specular inputs."""
+    the hostile frame with every entry of every family, random finite diffuse / specular
+    inputs."""
     import torch
     import lights_ref
     from vct import Context, scenes
@@ -421,8 +425,10 @@ def _consumer_setup(n=16):
     fr = TI.build(clean, ref["g0"], ref["E"], n, E_FAMILIES, exclude=E_EXCLUDE)
     placed = {w[0] for w in fr.where}
     want = {e.name for e in TI.catalogue(ref["g0"], ref["E"], n) if e.family in E_FAMILIES} - set(E_EXCLUDE)
-    assert placed == want and len(want) == 47
-    assert np.isfinite(fr.pos[..., :3]).all() and np.isfinite(fr.nrm).all() and np.abs(fr.pos[..., :3]).max() < 1e5
+    assert placed == want and len(want) == 47 + 2 + 10
+    assert {"pos_big+", "pos_big-", "p_posinf_x", "p_neginf_y", "p_nan_x", "p_nan_y", "p_nan_z", "n_nan_x",
+            "n_posinf_y", "n_neginf_z"} <= placed
+    assert np.isnan(fr.pos[..., :3]).sum() >= 3 and np.isinf(fr.pos[..., :3]).sum() >= 2 and np.isnan(fr.nrm).sum() >= 3
     dev = torch.device("cuda")
     gb = [torch.from_numpy(a).to(dev) for a in (fr.pos, fr.nrm, fr.alb)]
     gen = torch.Generator(device="cpu").manual_seed(3)
@@ -438,6 +444,15 @@ def _lin_same(got, want, fr, what):
     names = [(int(y), int(x), fr.names[fr.entry[y, x]] if fr.entry[y, x] >= 0 else "clean")
              for y, x in zip(ys[:12], xs[:12])]
     assert not d.any(), f"{what}: {int(d.sum())} pixels differ, first: {names}"
+
+
+def _inf_pixels(fr):
+    """The pixels of the INF_COLOUR entries (see the module docstring)."""
+    m = np.zeros((H, W), bool)
+    for name, y, x in fr.where:
+        if name in INF_COLOUR:
+            m[y, x] = True
+    return m
 
 
 def test_consumer_composite(gpu_ready, oracle_mod):
@@ -456,11 +471,12 @@ def test_consumer_composite(gpu_ready, oracle_mod):
     assert np.array_equal(ao.view(np.uint32), np.asarray(ref["grid"]["albedo_occ"], F).view(np.uint32))
     want_lin, want_rgba = oracle_mod.composite(16, ref["g0"], ref["E"], ao, fr.pos, fr.nrm, fr.alb, Dn, Sn,
                                                scenes.LIGHT_DIR, scenes.LIGHT_COLOR)
-    assert np.isfinite(want_lin).all()
+    inf_px = _inf_pixels(fr)
+    assert np.isfinite(want_lin[~inf_px]).all() and np.isposinf(want_lin[inf_px][:, :3]).all() and inf_px.any()
     _lin_same(lin.cpu().numpy(), want_lin, fr, "composite")
     got = rgba.cpu().numpy().view(np.uint32)
     for sh in (0, 8, 16, 24):
-        assert np.abs(((got >> sh) & 255).astype(np.int64) - ((want_rgba >> sh) & 255).astype(np.int64)).max() <= 1
+        assert np.abs(((got >> sh) & 255).astype(np.int64) - ((want_rgba >> sh) & 255).astype(np.int64))[~inf_px].max() <= 1
     for name, y, x in fr.where:
         if name == "w_negzero":
             assert want_lin[y, x, 3] == 0
@@ -480,7 +496,9 @@ def test_consumer_composite_lights(gpu_ready, oracle_mod):
     stats = []
     want = lights_ref.composite(16, ref["g0"], ref["E"], ref["grid"]["albedo_occ"], fr.pos, fr.nrm, fr.alb, Dn, Sn,
                                 ref["lights"], stats)
-    assert np.isfinite(want).all() and all(s["walked"] for s in stats) and sum(s["blocked"] for s in stats) > 100
+    inf_px = _inf_pixels(fr)
+    assert np.isfinite(want[~inf_px]).all() and np.isposinf(want[inf_px][:, :3]).all()
+    assert all(s["walked"] for s in stats) and sum(s["blocked"] for s in stats) > 100
     _lin_same(lin.cpu().numpy(), want, fr, "composite_lights")
     ctx.close()
 

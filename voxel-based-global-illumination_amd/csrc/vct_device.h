@@ -122,6 +122,21 @@ __device__ __forceinline__ float dda_visibility(const unsigned long long* __rest
     }
 }
 
+// Shadow-walk receiver rule (vct_spec.h): a walk from a caller's receiver starts only if
+// 0 <= q_a < n holds in float32 on every axis, tested before any conversion; otherwise V = 1
+// and nothing is read.  A NaN fails the compares, -0.0f passes.  For every q an int holds this
+// is the walk's own floor(q) test, so no defined result changes; for the rest (NaN, +-inf,
+// |q| >= 2^31) it replaces a conversion whose result the language leaves open (v_cvt_i32_f32
+// turns NaN into 0: a start cell the pixel has nothing to do with, and in dda_visibility an
+// axis that can never move).  The guard stands at the receiver call sites (k_composite,
+// kl_composite<false, *>, the hard branch of ks_march), not in dda_visibility / dda_lim: K2's
+// callers (k2 walks of vct_voxelize.hip, kl_pairs / kl_walk of vct_lights.hip) pass a voxel
+// centre plus a K1 normal, finite and in range by K1's rule, and keep their code as it was.
+__device__ __forceinline__ bool walk_starts(int N, float qx, float qy, float qz) {
+    const float fn = (float)N;
+    return qx >= 0.0f && qx < fn && qy >= 0.0f && qy < fn && qz >= 0.0f && qz < fn;
+}
+
 __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
     return (ax * bx + ay * by) + az * bz;
 }

@@ -287,8 +287,11 @@ __global__ void __launch_bounds__(256) k_composite(CompK k) {
     const float ndl = dot3(N.x, N.y, N.z, k.lx, k.ly, k.lz);
     float dr = 0.0f, dg = 0.0f, db = 0.0f;
     if (ndl > 0.0f) {
-        const float vis = dda_visibility(k.bits, k.n, (P.x - k.g0x) * k.inv_h + N.x, (P.y - k.g0y) * k.inv_h + N.y,
-                                         (P.z - k.g0z) * k.inv_h + N.z, k.lx, k.ly, k.lz);
+        const float qx = (P.x - k.g0x) * k.inv_h + N.x, qy = (P.y - k.g0y) * k.inv_h + N.y,
+                    qz = (P.z - k.g0z) * k.inv_h + N.z;
+        // shadow-walk receiver rule (vct_spec.h): the float test before the walk's conversion
+        const float vis =
+            walk_starts(k.n, qx, qy, qz) ? dda_visibility(k.bits, k.n, qx, qy, qz, k.lx, k.ly, k.lz) : 1.0f;
         dr = ((A.x * k.cr) * ndl) * vis;
         dg = ((A.y * k.cg) * ndl) * vis;
         db = ((A.z * k.cb) * ndl) * vis;

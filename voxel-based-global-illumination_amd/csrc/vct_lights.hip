@@ -320,7 +320,8 @@ __global__ void __launch_bounds__(256) kl_composite(const CompK k, const LightSe
         if (!light_terms(L, k.h2, qx, qy, qz, N.x, N.y, N.z, lx, ly, lz, f, ndl, t_lim)) continue;
         float vis;
         if constexpr (VIS) vis = k.vis[(size_t)j * npx + i];
-        else vis = dda_lim(k.bits, k.n, qx, qy, qz, lx, ly, lz, t_lim);
+        else   // shadow-walk receiver rule (vct_spec.h): the float test before the walk's conversion
+            vis = walk_starts(k.n, qx, qy, qz) ? dda_lim(k.bits, k.n, qx, qy, qz, lx, ly, lz, t_lim) : 1.0f;
         dr = dr + (((A.x * L.cr) * ndl) * f) * vis;
         dg = dg + (((A.y * L.cg) * ndl) * f) * vis;
         db = db + (((A.z * L.cb) * ndl) * f) * vis;

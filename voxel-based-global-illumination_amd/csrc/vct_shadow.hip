@@ -109,7 +109,10 @@ __global__ void __launch_bounds__(64) ks_march(const ShadowK k, const LightSet s
         if (__builtin_amdgcn_ballot_w64(need) != 0ull) {
             const uint32_t slot = k.slot[j];
             if (slot == kHard) {
-                if (need) V = dda_lim(k.bits, k.n, qx, qy, qz, lx, ly, lz, t_lim);
+                // shadow-walk receiver rule (vct_spec.h): outside the float test V = 1, as the
+                // soft path's cone gives for the same pixel (0 steps)
+                if (need)
+                    V = walk_starts(k.n, qx, qy, qz) ? dda_lim(k.bits, k.n, qx, qy, qz, lx, ly, lz, t_lim) : 1.0f;
             } else {
                 const StepRow* tab = k.tabs + (size_t)slot * kShadowRows;
                 float a;
