@@ -52,12 +52,30 @@ const char* vcth_texture_error(const vcth_model* m, uint32_t i);
 #define VCTH_MAP_SPECULAR 0
 #define VCTH_MAP_NORMAL   1
 #define VCTH_MAP_HEIGHT   2
+#define VCTH_MAP_OPACITY  3   /* map_d, the opacity mask of include/vct_cutout.h (same option skipping): the fourth
+                               * slot of the shading list, read with vcth_material_opacity_map --
+                               * vcth_material_shading_map keeps its three slots and refuses any other */
 int vcth_material_shininess(const vcth_model* m, uint32_t i, float* ns);
 int vcth_material_shading_map(const vcth_model* m, uint32_t i, int slot, const char** path, int32_t* texture);
 uint32_t vcth_num_shading_textures(const vcth_model* m);
 int vcth_shading_texture(const vcth_model* m, uint32_t i, const uint8_t** rgba8, uint32_t* width, uint32_t* height,
                          const char** path);
 uint32_t vcth_num_shading_texture_errors(const vcth_model* m);
+/* Cutouts (include/vct_cutout.h).  d: the .mtl's dissolve factor (1 when absent); the channel
+ * count of a texture's file before its expansion to RGBA8 (stbi_load's comp), for the diffuse and
+ * for the shading list.  The rule a host applies to build a vct_cutout per material:
+ *   map_d with 4 channels       -> that texture, channel 3;
+ *   map_d with 1 or 3 channels  -> that texture, channel 0;
+ *   no map_d, a 4-channel map_Kd -> that map, channel 3;
+ *   else opaque.
+ * (vct_set_textures takes one list: a host appends the shading list to the diffuse list and
+ * offsets the shading indices by vcth_num_textures.) */
+/* map_d of material i: its path ("" = none) and its index in the SHADING texture list (-1: none,
+ * or it failed to load; failures are in the shading list's errors) */
+int vcth_material_opacity_map(const vcth_model* m, uint32_t i, const char** path, int32_t* texture);
+int vcth_material_dissolve(const vcth_model* m, uint32_t i, float* d);
+int vcth_texture_channels(const vcth_model* m, uint32_t i, int* comp);
+int vcth_shading_texture_channels(const vcth_model* m, uint32_t i, int* comp);
 const char* vcth_shading_texture_error(const vcth_model* m, uint32_t i);
 /* PNG decode as stbi_load(file, &w, &h, &comp, 0) (model.cpp:197): *data = h rows of
  * w * comp bytes (release with vcth_free_image).  Returns 0, or -1 with a message. */

@@ -1031,4 +1031,38 @@
  *    composites' own (tone01 and quant8 of csrc/vct_view.h) for every finite radiance >= 0.
  *  The section's literals (VCT_PRESENT_KEY0, VCT_SRGB_INV_GAMMA, VCT_EXPOSURE_LIMIT) stand with
  *  VCT_INV_GAMMA, above. */
+
+/* ---- cutouts (vct_voxelize_cutout* / vct_gbuffer_cutout_device, include/vct_cutout.h;
+ * tests/cutout_ref.py restates it) ---------------------------------------------------------------
+ *  A binary alpha test: a point of a masked triangle exists or it does not.
+ *  M_c(u, v), c = 0 .. 3 (r, g, b, a): the formula T(u, v) of "diffuse maps", unchanged, on
+ *    channel c of the RGBA8 texel: the same wrap, texel-centre convention and lerp(a, b, f) =
+ *    fmaf(f, b - a, a); texel value byte / 255.0f; a non-finite coordinate becomes 0; base level
+ *    only.
+ *  A material is MASKED when its vct_cutout entry has map >= 0.  A point of one of its triangles
+ *    with TexCoords (u, v) is COVERED iff M_channel(u, v) >= cutoff, compared in float32 (the
+ *    texels are bytes, so M is never a NaN).  A masked triangle whose vertex record holds no
+ *    TexCoords (uv_offset not a multiple of 4, or uv_offset + 8 > vertex_stride) is opaque.
+ *  Input rule, the table (host memory, checked before any launch).  VCT_EINVAL, the context --
+ *    the previous grid and mesh included -- left as it was: map < -1 or >= the texture count;
+ *    channel > 3; a cutoff that is not finite or outside 0 < cutoff <= 1; reserved != 0; a table
+ *    with n_materials == 0.  Every other input: the rules of vct_voxelize_textured*, but that with
+ *    a table that masks a material tri_material[t] >= n_materials is K1's index error whether
+ *    or not a Kd table or a diffuse-map table is given (the table is indexed by the material).
+ *  K1.  A (triangle, voxel) pair of a masked triangle that passes the 13-axis SAT contributes iff
+ *    the point K1 uses for the diffuse map -- (b1, b2) of the voxel centre projected onto the plane
+ *    and clamped into the triangle, uv = the TexCoords form, both of "diffuse maps" -- is
+ *    covered.  A pair that is not covered adds nothing: no sums, no count, no occupancy bit.  A
+ *    covered pair adds what vct_voxelize_textured adds (Kd x diffuse map, or Kd).  Candidate
+ *    counts and offsets are taken before the SAT and do not change.  Only integer pair sums
+ *    enter, so the grid is exact whatever the order.
+ *  G-buffer.  A candidate (triangle k, t) of a pixel's ray is ACCEPTED iff t > 0 and triangle k is
+ *    opaque or the point at the Moller-Trumbore (b1, b2) of that hit (ray_tri_bary) is covered.
+ *    The pixel's hit is the smallest accepted t, ties to the lower triangle index.  near / far
+ *    are then tested on that one hit, as the "G-buffer input rule" says: an accepted hit nearer
+ *    than near still hides what is behind it, a rejected candidate hides nothing.  The records
+ *    are those of vct_gbuffer_raster_device (flat) or "shading attributes" (shaded) for that
+ *    (k, t).  A mask index >= the CURRENT texture count (a later, smaller vct_set_textures) is no
+ *    mask: the shading rule for a stale map.  Dynamic-layer triangles are opaque.
+ *  No new literal. */
 #endif /* VCT_SPEC_H */

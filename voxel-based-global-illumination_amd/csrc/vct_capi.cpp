@@ -335,6 +335,7 @@ void vct_destroy(vct_ctx* c) {
     fog_free(c);
     env_free(c);
     shading_free(c);
+    cutout_free(c);
     for (auto& s : c->scratch)
         if (s.p) (void)hipFree(s.p);
     for (auto& ss : c->k4s)
@@ -394,10 +395,13 @@ static vct_status voxelize_args(vct_ctx* c, const void* verts, uint32_t stride, 
 
 // K1 on device-resident geometry; `derr` (device int) receives the index-range and Kd flags.
 // dmap (device, may be NULL): each material's diffuse map (vct_voxelize_textured).
+// cutout (HOST, may be NULL): a checked table with a masked material, for a vertex record that
+// holds TexCoords (vct_voxelize_cutout, cutout_table)
 static vct_status voxelize_dev(vct_ctx* c, const void* dv, uint32_t stride, uint32_t n_verts, const uint32_t* di,
                                uint32_t n_tri, const uint32_t* dm, const float4* dk, uint32_t n_mat,
-                               const int32_t* dmap, uint32_t uv_offset, int* derr) {
+                               const int32_t* dmap, uint32_t uv_offset, int* derr, const vct_cutout* cutout = nullptr) {
     Mesh& m = c->mesh;
+    const bool uvs = dmap || cutout;   // Mesh::uv holds the textured and the masked triangles' TexCoords
     const size_t tri_bytes = (size_t)(n_tri ? n_tri : 1) * 4 * sizeof(float4);
     if (m.cap < tri_bytes) {
         VCT_HIP(hipStreamSynchronize(c->stream), "sync");
@@ -408,7 +412,7 @@ static vct_status voxelize_dev(vct_ctx* c, const void* dv, uint32_t stride, uint
         m.cap = tri_bytes;
     }
     const size_t uv_bytes = (size_t)(n_tri ? n_tri : 1) * 2 * sizeof(float4);
-    if (dmap && m.uv_cap < uv_bytes) {
+    if (uvs && m.uv_cap < uv_bytes) {
         VCT_HIP(hipStreamSynchronize(c->stream), "sync");
         if (m.uv) (void)hipFree(m.uv);
         m.uv = nullptr;
@@ -417,7 +421,7 @@ static vct_status voxelize_dev(vct_ctx* c, const void* dv, uint32_t stride, uint
         m.uv_cap = uv_bytes;
     }
     m.n_tri = n_tri;
-    m.textured = dmap != nullptr;
+    m.textured = uvs;
     // Everything derived from the previous occupancy is invalid from here on, and stays so
     // if a step below fails part way (K1 has already rewritten the accumulators, the
     // occupied list and level 0 by then): only the success path sets `voxelized` again
@@ -426,10 +430,15 @@ static vct_status voxelize_dev(vct_ctx* c, const void* dv, uint32_t stride, uint
     g.k2_coarse_ok = g.k3_sparse_ok = g.zm_valid = false;
     g.k3_live_bz = 0;
     ++c->grid_epoch;
+    CutoutPass pass{}, *cut = nullptr;
+    if (cutout) {   // (a voxelization without a table drops the previous one by its epoch)
+        VCT_HIP(cutout_begin(c, cutout, n_mat, n_tri, &pass), "cutout table");
+        cut = &pass;
+    }
     int herr = 0;
     for (bool packed : {true, false}) {
         VCT_HIP(hipMemsetAsync(derr, 0, 4, c->stream), "memset err");
-        VCT_HIP(launch_voxelize(c, dv, stride, n_verts, di, n_tri, dm, dk, n_mat, dmap, uv_offset, derr, packed),
+        VCT_HIP(launch_voxelize(c, dv, stride, n_verts, di, n_tri, dm, dk, n_mat, dmap, uv_offset, derr, packed, cut),
                 "voxelize");
         // the K3 live list of a packed pass is the repeat's too (same occupancy), but it is
         // queued before the one read-back so that its count arrives with the error word
@@ -444,6 +453,19 @@ static vct_status voxelize_dev(vct_ctx* c, const void* dv, uint32_t stride, uint
     if (herr & kK1ErrKd) return fail(c, VCT_EINVAL, kKdMessage);
     if (herr & kK1ErrIndex) return fail(c, VCT_EINVAL, "vertex, material or diffuse-map index out of range");
     g.voxelized = true;
+    if (cutout) cutout_commit(c, cutout, n_mat, n_tri);
+    return VCT_OK;
+}
+
+// The cutout table of a vct_voxelize_cutout* call: *use = the table where the pass needs it
+// (a masked material, and a vertex record that holds TexCoords), else NULL: every triangle is
+// opaque and the call is vct_voxelize_textured*'s
+static vct_status cutout_table(vct_ctx* c, const vct_cutout* table, uint32_t n_mat, uint32_t stride, uint32_t uv_offset,
+                               const vct_cutout** use) {
+    *use = nullptr;
+    if (const char* bad = cutout_table_error(c, table, n_mat)) return fail(c, VCT_EINVAL, bad);
+    const bool has_uv = uv_offset % 4 == 0 && (uint64_t)uv_offset + 8 <= stride;
+    if (has_uv && cutout_masked(table, n_mat)) *use = table;
     return VCT_OK;
 }
 
@@ -457,10 +479,12 @@ static vct_status map_args(vct_ctx* c, const int32_t* map, uint32_t n_mat, uint3
 
 static vct_status voxelize_host(vct_ctx* c, const void* verts, uint32_t stride, uint32_t n_verts,
                                 const uint32_t* idx, uint32_t n_idx, const uint32_t* tri_mat, const float* kd4,
-                                const int32_t* map, uint32_t n_mat, uint32_t uv_offset) {
+                                const int32_t* map, uint32_t n_mat, uint32_t uv_offset,
+                                const vct_cutout* cutout = nullptr) {
     vct_status st = voxelize_args(c, verts, stride, n_idx, idx, kd4, n_mat);
     if (st != VCT_OK) return st;
     if ((st = map_args(c, map, n_mat, stride, uv_offset)) != VCT_OK) return st;
+    if ((st = cutout_table(c, cutout, n_mat, stride, uv_offset, &cutout)) != VCT_OK) return st;
     if (map)
         for (uint32_t i = 0; i < n_mat; ++i)
             if (map[i] < -1 || (map[i] >= 0 && (uint32_t)map[i] >= c->tex.n))
@@ -487,20 +511,22 @@ static vct_status voxelize_host(vct_ctx* c, const void* verts, uint32_t stride, 
     if ((st = stage_mesh(c, ms, verts, (size_t)stride * n_verts, idx, n_idx, tri_mat, kd4, "kd", map, n_mat)) != VCT_OK)
         return st;
     return voxelize_dev(c, ms.verts.p, stride, n_verts, (const uint32_t*)ms.idx.p, n_tri, (const uint32_t*)ms.mat.p,
-                        (const float4*)ms.mats.p, n_mat, (const int32_t*)ms.map.p, uv_offset, (int*)derr.p);
+                        (const float4*)ms.mats.p, n_mat, (const int32_t*)ms.map.p, uv_offset, (int*)derr.p, cutout);
 }
 
 static vct_status voxelize_device(vct_ctx* c, const void* verts, uint32_t stride, uint32_t n_verts,
                                   const uint32_t* idx, uint32_t n_idx, const uint32_t* tri_mat, const float* kd4,
-                                  const int32_t* map, uint32_t n_mat, uint32_t uv_offset) {
+                                  const int32_t* map, uint32_t n_mat, uint32_t uv_offset,
+                                  const vct_cutout* cutout = nullptr) {
     vct_status st = voxelize_args(c, verts, stride, n_idx, idx, kd4, n_mat);
     if (st != VCT_OK) return st;
     if ((st = map_args(c, map, n_mat, stride, uv_offset)) != VCT_OK) return st;
+    if ((st = cutout_table(c, cutout, n_mat, stride, uv_offset, &cutout)) != VCT_OK) return st;
     if ((kd4 && ((uintptr_t)kd4 & 15)) || ((uintptr_t)verts & 3) || ((uintptr_t)map & 3))
         return fail(c, VCT_EINVAL, "material_kd4 must be 16-byte, verts and material_map 4-byte aligned");
     if (!c->k1_err) VCT_HIP(hipMalloc((void**)&c->k1_err, 4), "hipMalloc err");
     return voxelize_dev(c, verts, stride, n_verts, idx, n_idx / 3, tri_mat, (const float4*)kd4, n_mat, map, uv_offset,
-                        c->k1_err);
+                        c->k1_err, cutout);
 }
 
 vct_status vct_voxelize(vct_ctx* c, const void* verts, uint32_t stride, uint32_t n_verts,
@@ -525,6 +551,18 @@ vct_status vct_voxelize_textured_device(vct_ctx* c, const void* verts, uint32_t 
                                         const uint32_t* idx, uint32_t n_idx, const uint32_t* tri_mat,
                                         const float* kd4, const int32_t* map, uint32_t n_mat, uint32_t uv_offset) {
     return voxelize_device(c, verts, stride, n_verts, idx, n_idx, tri_mat, kd4, map, n_mat, uv_offset);
+}
+
+vct_status vct_voxelize_cutout(vct_ctx* c, const void* verts, uint32_t stride, uint32_t n_verts, const uint32_t* idx,
+                               uint32_t n_idx, const uint32_t* tri_mat, const float* kd4, const int32_t* map,
+                               const vct_cutout* cutout, uint32_t n_mat, uint32_t uv_offset) {
+    return voxelize_host(c, verts, stride, n_verts, idx, n_idx, tri_mat, kd4, map, n_mat, uv_offset, cutout);
+}
+
+vct_status vct_voxelize_cutout_device(vct_ctx* c, const void* verts, uint32_t stride, uint32_t n_verts,
+                                      const uint32_t* idx, uint32_t n_idx, const uint32_t* tri_mat, const float* kd4,
+                                      const int32_t* map, const vct_cutout* cutout, uint32_t n_mat, uint32_t uv_offset) {
+    return voxelize_device(c, verts, stride, n_verts, idx, n_idx, tri_mat, kd4, map, n_mat, uv_offset, cutout);
 }
 
 vct_status vct_set_textures(vct_ctx* c, const vct_texture* tex, uint32_t n) {

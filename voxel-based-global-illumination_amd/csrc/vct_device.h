@@ -178,6 +178,41 @@ __device__ __forceinline__ void tex_sample(const uint32_t* __restrict__ texels, 
     r = out[0]; g = out[1]; b = out[2];
 }
 
+// The same sample in two steps, for a caller that wants another channel, or several of one
+// fetch (vct_spec.h "cutouts": M_c is T on channel c = 0..3): tex_tap = tex_sample's address
+// arithmetic and its four texels, tex_channel = its two lerps on one channel.  Channel for
+// channel the operations, and so the bits, are tex_sample's
+struct TexTap {
+    uint32_t p00, p10, p01, p11;
+    float ax, ay;
+};
+
+__device__ __forceinline__ TexTap tex_tap(const uint32_t* __restrict__ texels, TexDesc d, float u, float v) {
+    if (!__builtin_isfinite(u)) u = 0.0f;
+    if (!__builtin_isfinite(v)) v = 0.0f;
+    const float fu = u - floorf(u), fv = v - floorf(v);
+    const float s = fu * (float)d.w - 0.5f, t = fv * (float)d.h - 0.5f;
+    const float sx = floorf(s), sy = floorf(t);
+    int x0 = (int)sx, y0 = (int)sy;          // in [-1, w - 1] / [-1, h - 1]
+    int x1 = x0 + 1, y1 = y0 + 1;
+    if (x0 < 0) x0 += (int)d.w;
+    if (y0 < 0) y0 += (int)d.h;
+    if (x1 >= (int)d.w) x1 -= (int)d.w;
+    if (y1 >= (int)d.h) y1 -= (int)d.h;
+    const uint32_t* base = texels + d.off;
+    TexTap q;
+    q.p00 = base[(size_t)y0 * d.w + x0]; q.p10 = base[(size_t)y0 * d.w + x1];
+    q.p01 = base[(size_t)y1 * d.w + x0]; q.p11 = base[(size_t)y1 * d.w + x1];
+    q.ax = s - sx; q.ay = t - sy;
+    return q;
+}
+
+__device__ __forceinline__ float tex_channel(const TexTap& q, uint32_t c) {
+    const float t00 = (float)((q.p00 >> (8 * c)) & 255u) / 255.0f, t10 = (float)((q.p10 >> (8 * c)) & 255u) / 255.0f;
+    const float t01 = (float)((q.p01 >> (8 * c)) & 255u) / 255.0f, t11 = (float)((q.p11 >> (8 * c)) & 255u) / 255.0f;
+    return tex_lerp(tex_lerp(t00, t10, q.ax), tex_lerp(t01, t11, q.ax), q.ay);
+}
+
 // K1's (b1, b2): voxel centre (cx, cy, cz) projected onto the plane of q[9], clamped
 // into the triangle (vct_spec.h); q in voxel units
 __device__ __forceinline__ void tri_bary(const float* __restrict__ q, float cx, float cy, float cz, float& b1,

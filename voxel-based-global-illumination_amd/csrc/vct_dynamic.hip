@@ -345,8 +345,10 @@ vct_status dynamic_update(vct_ctx* c, const void* d_verts, uint32_t stride, uint
     g.k2_coarse_ok = g.k3_sparse_ok = g.zm_valid = false;
     g.k3_live_bz = 0;
     const bool shaded = shading_live(c);   // the shading set describes the static triangles, which stay
+    const bool cutout = cutout_live(c);    // and so does the cutout table (the layer's triangles are opaque)
     ++c->grid_epoch;
     if (shaded) c->shade.epoch = c->grid_epoch;
+    if (cutout) c->cut.epoch = c->grid_epoch;
     d.live = false;
     m.n_tri = n_static;
     if (!had) {   // no layer in place: whatever the record sets hold belongs to an earlier grid

@@ -1,7 +1,7 @@
-// vct_gbuffer.h — what the G-buffer passes of vct_frame.hip and the shaded pass of
-// vct_shading.hip share: the kernel records, the Moller-Trumbore test and its barycentrics.
-// One definition each, so the passes cannot drift apart.  Internal to the including
-// translation unit.
+// vct_gbuffer.h — what the G-buffer passes of vct_frame.hip, the shaded pass of
+// vct_shading.hip and the cutout pass of vct_cutout.hip share: the kernel records, the
+// Moller-Trumbore test and its barycentrics, the flat texel writer.  One definition each, so
+// the passes cannot drift apart.  Internal to the including translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vct_internal.h"
@@ -74,6 +74,38 @@ __device__ __forceinline__ void ray_tri_bary(float4 v0, float4 e1, float4 e2, fl
     u = dot3(tx, ty, tz, pvx, pvy, pvz) * inv;
     const float qx = ty * e1.z - tz * e1.y, qy = tz * e1.x - tx * e1.z, qz = tx * e1.y - ty * e1.x;
     v = dot3(dx, dy, dz, qx, qy, qz) * inv;
+}
+
+// G-buffer texel of the nearest hit (shared by the brute-force, the binned and the cutout pass)
+__device__ __forceinline__ void write_gbuffer(const RayK& k, int x, int y, float dx, float dy, float dz, float best,
+                                              int hit) {
+    const size_t p = (size_t)y * k.w + x;
+    const float depth = best * dot3(dx, dy, dz, k.fx, k.fy, k.fz);
+    if (hit < 0 || depth < k.near_p || depth > k.far_p) {
+        k.pos[p] = make_float4(0, 0, 0, 0);
+        k.nrm[p] = make_float4(0, 0, 0, 0);
+        k.alb[p] = make_float4(0, 0, 0, k.rough);
+        return;
+    }
+    const float4 e1 = k.tri[(size_t)hit * 4 + 1], e2 = k.tri[(size_t)hit * 4 + 2], kd = k.tri[(size_t)hit * 4 + 3];
+    float nx = e1.y * e2.z - e1.z * e2.y, ny = e1.z * e2.x - e1.x * e2.z, nz = e1.x * e2.y - e1.y * e2.x;
+    const float nl = sqrtf(dot3(nx, ny, nz, nx, ny, nz));
+    nx /= nl; ny /= nl; nz /= nl;
+    if (dot3(nx, ny, nz, dx, dy, dz) > 0.0f) { nx = -nx; ny = -ny; nz = -nz; }
+    k.pos[p] = make_float4(k.px + dx * best, k.py + dy * best, k.pz + dz * best, 1.0f);
+    k.nrm[p] = make_float4(nx, ny, nz, 0.0f);
+    float ar = kd.x, ag = kd.y, ab = kd.z;
+    const int tex = __float_as_int(kd.w);
+    if (k.uv && tex >= 0 && (uint32_t)tex < k.n_tex) {   // albedo = Kd x T(uv of the hit)
+        float b1, b2, u, v, tr, tg, tb;
+        ray_tri_bary(k.tri[(size_t)hit * 4], e1, e2, k.px, k.py, k.pz, dx, dy, dz, b1, b2);
+        const float4 a = k.uv[(size_t)hit * 2], b = k.uv[(size_t)hit * 2 + 1];
+        const float uv[6] = {a.x, a.y, a.z, a.w, b.x, b.y};
+        tri_uv(uv, b1, b2, u, v);
+        tex_sample(k.texels, k.tdesc[tex], u, v, tr, tg, tb);
+        ar = kd.x * tr; ag = kd.y * tg; ab = kd.z * tb;
+    }
+    k.alb[p] = make_float4(ar, ag, ab, k.rough);
 }
 
 }  // namespace

@@ -228,6 +228,21 @@ struct Shading {
     uint32_t epoch = 0;
 };
 
+// The cutout table of the mesh (vct_cutout.hip; vct_spec.h "cutouts").  Per static triangle one
+// word pair for the G-buffer pass: x = the mask word 4 * mask map + channel (0xFFFFFFFF: opaque),
+// y = the cutoff's bits; the TexCoords of every masked triangle are in Mesh::uv.  It belongs to
+// the static triangles of the voxelization `epoch`: a dynamic update carries a live table over to
+// its new epoch (vct_dynamic.hip; the layer's triangles lie past n_tri and are opaque), every
+// other voxelization or load drops it.
+struct Cutout {
+    uint2* tri = nullptr;            // [n_tri]
+    vct_cutout* table = nullptr;     // [n_mat] the host's table, for K1's triangle setup
+    size_t tri_cap = 0, table_cap = 0;   // bytes
+    uint32_t n_tri = 0, n_masked = 0;
+    bool live = false;
+    uint32_t epoch = 0;
+};
+
 // K4's per-launch scratch, one set per stream: K4 launches on different streams may run
 // concurrently (a host that overlaps consecutive frames), so the cone-split hand-over
 // and the ray-reorder buffers belong to the stream, not to the context.
@@ -362,6 +377,7 @@ struct vct_ctx {
     vct::Fog fog;                       // scatter volume of vct_build_fog
     vct::Env env;                       // map and mips of vct_set_env
     vct::Shading shade;                 // attribute records and materials of vct_set_shading
+    vct::Cutout cut;                    // per-triangle masks of vct_voxelize_cutout*
     uint32_t grid_epoch = 0;            // bumped by every voxelization (a new scene for the tuner)
     vct::StepRow* step_tab = nullptr;   // [kMaxStepRows] diffuse-cone step table (device)
     unsigned* spec_keys = nullptr;      // [2 * kSpecSlots]: specular table keys (~0u free), then states
@@ -474,10 +490,43 @@ inline vct_status stage_mesh(vct_ctx* c, MeshStage& s, const void* verts, size_t
 constexpr int kK1ErrIndex = 1, kK1ErrRedo = 2, kK1ErrKd = 4;
 // the text of a Kd that breaks the K1 input rule, from the host check or the device flag
 constexpr const char* kKdMessage = "material_kd4: Kd not finite or |Kd| >= 32768";
+// cut (vct_voxelize_cutout*): the pass runs vct_cutout.hip's triangle setup and candidates
+// kernels in place of K1's own; everything around them is the same pass
+struct CutoutPass {
+    const vct_cutout* table;   // device, n_mat entries
+    uint2* tri;                // device, n_tri entries: Cutout::tri
+};
 hipError_t launch_voxelize(vct_ctx* c, const void* d_verts,
                            uint32_t stride, uint32_t n_verts, const uint32_t* d_idx, uint32_t n_tri,
                            const uint32_t* d_mat, const float4* d_kd, uint32_t n_mat, const int32_t* d_map,
-                           uint32_t uv_offset, int* d_err, bool packed = true);
+                           uint32_t uv_offset, int* d_err, bool packed = true, const CutoutPass* cut = nullptr);
+// K1 with cutouts (vct_cutout.hip), called by the pass above.  The records are K1's (TriGeom,
+// TriFix, TriUV of vct_voxel_sat.h, which are internal to each translation unit: void* here)
+struct K1SetupArgs {
+    const char* verts; uint32_t stride, n_verts; const uint32_t* idx; uint32_t n_tri; const uint32_t* mat;
+    const float4* kd; uint32_t n_mat; const int32_t* map; uint32_t uv_offset, n_tex; int n;
+    float g0x, g0y, g0z, inv_h;
+    void *geom, *fix, *tuv;
+    unsigned long long* counts;
+    float4 *mesh_tri, *mesh_uv;
+    int* err;
+    uint32_t* maxabs;
+};
+void launch_cutout_setup(vct_ctx* c, const K1SetupArgs& a, const CutoutPass& cut);
+void launch_cutout_candidates(vct_ctx* c, uint32_t blocks, bool packed, const void* geom, const void* fix,
+                              const unsigned long long* offs, uint32_t n_tri, const unsigned long long* total,
+                              const uint32_t* starts, const void* tuv);
+// the table rule of vct_voxelize_cutout* (vct_spec.h "cutouts") on the host: nullptr, or what is wrong
+const char* cutout_table_error(const vct_ctx* c, const vct_cutout* table, uint32_t n_mat);
+// masked entries of a table (0 for NULL)
+uint32_t cutout_masked(const vct_cutout* table, uint32_t n_mat);
+// Before a cutout pass: grows Cutout::tri and Cutout::table, queues the table's upload on the ctx
+// stream and fills *pass.  The table is dropped (live = false) until cutout_commit
+hipError_t cutout_begin(vct_ctx* c, const vct_cutout* table, uint32_t n_mat, uint32_t n_tri, CutoutPass* pass);
+// after the pass has succeeded: the table belongs to the current grid_epoch
+void cutout_commit(vct_ctx* c, const vct_cutout* table, uint32_t n_mat, uint32_t n_tri);
+inline bool cutout_live(const vct_ctx* c) { return c->cut.live && c->cut.epoch == c->grid_epoch; }
+void cutout_free(vct_ctx* c);
 // grid dumps: K1 records [cnt][7] int64 (albedo rgb, normal xyz sums, count) of the voxels
 // d_idx (device) -- read out of the accumulators, or written back into them after the
 // previous voxelization's sparse reset (bits, occupied list and resolved voxels rebuilt)

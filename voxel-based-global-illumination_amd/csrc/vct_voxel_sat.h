@@ -27,6 +27,18 @@ struct TriGeom {      // 64 B
     uint32_t pad;
 };
 
+// K1's per-triangle records beside TriGeom (vct_voxelize.hip; vct_cutout.hip fills the pads)
+struct TriFix {       // 64 B
+    long long fix[6]; // albedo rgb, face normal xyz in 16.16 fixed point
+    long long tex;    // diffuse map of the triangle's material (-1: albedo = Kd, fix[0..2])
+    long long pad;    // K1 with cutouts: the mask word, 4 * mask map + channel (-1: opaque); else 0
+};
+struct TriUV {        // 48 B, textured (K1 with cutouts: and masked) triangles only
+    float uv[6];      // TexCoords of the three vertices
+    float kd[3];      // material Kd (albedo = Kd x T(uv) per hit)
+    uint32_t pad[3];  // K1 with cutouts: [0] = the cutoff's bits; else 0
+};
+
 __device__ __forceinline__ float fmin3(float a, float b, float c) { return fminf(fminf(a, b), c); }
 __device__ __forceinline__ float fmax3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
 

@@ -41,16 +41,7 @@ extern "C" int vct_debug_k2_waves_clear() {
 namespace vct {
 namespace {
 
-struct TriFix {       // 64 B
-    long long fix[6]; // albedo rgb, face normal xyz in 16.16 fixed point
-    long long tex;    // diffuse map of the triangle's material (-1: albedo = Kd, fix[0..2])
-    long long pad;
-};
-struct TriUV {        // 48 B, textured triangles only
-    float uv[6];      // TexCoords of the three vertices
-    float kd[3];      // material Kd (albedo = Kd x T(uv) per hit)
-    uint32_t pad[3];
-};
+// (TriFix and TriUV are vct_voxel_sat.h's, shared with vct_cutout.hip)
 
 __global__ void __launch_bounds__(256) k1_tri_setup(
     const char* __restrict__ verts, uint32_t stride, uint32_t n_verts,
@@ -449,21 +440,22 @@ __global__ void __launch_bounds__(256) k2_inject(const float4* __restrict__ albe
 // synchronisation) and then repeats the pass unpacked.
 hipError_t voxelize_pass(vct_ctx* c, const void* d_verts, uint32_t stride, uint32_t n_verts, const uint32_t* d_idx,
                          uint32_t n_tri, const uint32_t* d_mat, const float4* d_kd, uint32_t n_mat,
-                         const int32_t* d_map, uint32_t uv_offset, int* d_err, bool packed) {
+                         const int32_t* d_map, uint32_t uv_offset, int* d_err, bool packed, const CutoutPass* cut) {
     Grid& g = c->grid;
     hipStream_t s = c->stream;
     const size_t nv = (size_t)g.n * g.n * g.n;
     hipError_t e;
-    // the head: total, max|value|; the tail: the textured triangles' UVs
+    // the head: total, max|value|; the tail: the textured (and, with cutouts, the masked) triangles' UVs
+    const bool uvs = d_map || cut;
     TriTemps tt;
-    if ((e = tri_temps(c, n_tri, sizeof(TriFix), d_map ? sizeof(TriUV) * (size_t)n_tri : 0, tt)) != hipSuccess) return e;
+    if ((e = tri_temps(c, n_tri, sizeof(TriFix), uvs ? sizeof(TriUV) * (size_t)n_tri : 0, tt)) != hipSuccess) return e;
     TriGeom* geom = tt.geom;
     TriFix* fix = (TriFix*)tt.fix;
     unsigned long long* cnt = tt.counts;
     unsigned long long* offs = tt.offs;
     unsigned long long* total = (unsigned long long*)tt.head;
     uint32_t* maxabs = (uint32_t*)(total + 1);
-    TriUV* tuv = d_map ? (TriUV*)tt.tail : nullptr;
+    TriUV* tuv = uvs ? (TriUV*)tt.tail : nullptr;
 
     // sparse reset of the previous voxelization (its occupied list), then the bits
     const size_t nwords = nv / 64;
@@ -476,10 +468,15 @@ hipError_t voxelize_pass(vct_ctx* c, const void* d_verts, uint32_t stride, uint3
     bool use_packed = false;
     g.k1_maxabs = 0;
     if (n_tri > 0) {
-        hipLaunchKernelGGL(k1_tri_setup, dim3((n_tri + 255) / 256), dim3(256), 0, s,
-                           (const char*)d_verts, stride, n_verts, d_idx, n_tri, d_mat, d_kd, n_mat, d_map,
-                           uv_offset, c->tex.n, (int)g.n, g.g0[0], g.g0[1], g.g0[2], g.inv_h, geom, fix, tuv, cnt,
-                           c->mesh.tri, c->mesh.uv, d_err, maxabs);
+        if (cut)
+            launch_cutout_setup(c, K1SetupArgs{(const char*)d_verts, stride, n_verts, d_idx, n_tri, d_mat, d_kd, n_mat,
+                                               d_map, uv_offset, c->tex.n, (int)g.n, g.g0[0], g.g0[1], g.g0[2], g.inv_h,
+                                               geom, fix, tuv, cnt, c->mesh.tri, c->mesh.uv, d_err, maxabs}, *cut);
+        else
+            hipLaunchKernelGGL(k1_tri_setup, dim3((n_tri + 255) / 256), dim3(256), 0, s,
+                               (const char*)d_verts, stride, n_verts, d_idx, n_tri, d_mat, d_kd, n_mat, d_map,
+                               uv_offset, c->tex.n, (int)g.n, g.g0[0], g.g0[1], g.g0[2], g.inv_h, geom, fix, tuv, cnt,
+                               c->mesh.tri, c->mesh.uv, d_err, maxabs);
         launch_count_scan(s, cnt, offs, tt.tiles, n_tri, total);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         // the candidate total is only known on the device: read it back to size the grid
@@ -499,7 +496,9 @@ hipError_t voxelize_pass(vct_ctx* c, const void* d_verts, uint32_t stride, uint3
             uint32_t blocks;
             uint32_t* starts;
             if ((e = launch_bucket_starts(c, offs, n_tri, total, h_total, &blocks, &starts)) != hipSuccess) return e;
-            if (use_packed)
+            if (cut)
+                launch_cutout_candidates(c, blocks, use_packed, geom, fix, offs, n_tri, total, starts, tuv);
+            else if (use_packed)
                 hipLaunchKernelGGL(k1_candidates<true>, dim3(blocks), dim3(256), 0, s, geom, fix, offs,
                                    n_tri, total, (int)g.n, g.accum, g.occ_bits, starts, tuv, c->tex.texels,
                                    c->tex.desc);
@@ -531,13 +530,13 @@ hipError_t voxelize_pass(vct_ctx* c, const void* d_verts, uint32_t stride, uint3
 hipError_t launch_voxelize(vct_ctx* c, const void* d_verts, uint32_t stride,
                            uint32_t n_verts, const uint32_t* d_idx, uint32_t n_tri, const uint32_t* d_mat,
                            const float4* d_kd, uint32_t n_mat, const int32_t* d_map, uint32_t uv_offset,
-                           int* d_err, bool packed) {
+                           int* d_err, bool packed, const CutoutPass* cut) {
     static const bool packed_env = [] {
         const char* v = getenv("VCT_K1_PACKED");
         return !(v && strcmp(v, "0") == 0);
     }();
     return voxelize_pass(c, d_verts, stride, n_verts, d_idx, n_tri, d_mat, d_kd, n_mat, d_map, uv_offset, d_err,
-                         packed && packed_env);
+                         packed && packed_env, cut);
 }
 
 namespace {

@@ -57,6 +57,10 @@
 //            map (map_Kn, else the map_Bump / bump slot) go through vct_set_shading and
 //            vct_gbuffer_shaded_device, and vct_specular_tint_device tints the specular plane before
 //            the composite; absent: face normals, one roughness, an untinted specular plane;
+//   --cutouts: [=CUTOFF, default 0.5] alpha cutouts (include/vct_cutout.h): a material's map_d (channel 3
+//            of a four-channel file, else channel 0), or else the alpha of a four-channel map_Kd, is a
+//            binary mask: the model goes through vct_voxelize_cutout and the frame through
+//            vct_gbuffer_cutout_device when some material is masked; absent: the masks are ignored;
 //   --dynamic: a second model, voxelized as the context's dynamic layer (include/vct_dynamic.h)
 //            on top of the first one's grid; Kd materials only (its diffuse maps are not loaded).
 //            --dynamic-offset: a world-space translation applied after the model matrix of
@@ -285,6 +289,7 @@ int main(int argc, char** argv) {
     std::vector<vct_light> lights;
     float shadow_tan = 0.0f;
     bool has_sky = false, sky_view = false, shaded = false;
+    float cutout = 0.0f;
     vct_sky sky{};
     bool has_env = false;
     std::vector<float> env_texels;
@@ -320,6 +325,8 @@ int main(int argc, char** argv) {
         }
         else if (a == "--sky-view") sky_view = true;
         else if (a == "--shaded") shaded = true;
+        else if (a == "--cutouts") cutout = 0.5f;
+        else if (a.rfind("--cutouts=", 0) == 0) cutout = (float)atof(a.c_str() + 10);
         else if (a == "--env" || a.rfind("--env=", 0) == 0) {
             const std::string spec = a == "--env" ? (i + 1 < argc ? argv[++i] : "") : a.substr(6);
             std::string why;
@@ -395,7 +402,7 @@ int main(int argc, char** argv) {
     if (sky_view && !has_sky && !has_env) { std::fprintf(stderr, "--sky-view needs --sky Z[:H[:G]] or --env FILE[:SCALE]\n"); return 2; }
     if (pos.empty()) {
         std::fprintf(stderr, "usage: %s model.obj [grid] [width] [height] [frames] [out.ppm] [devices] "
-                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] [--sky Z[:H[:G]]] [--env FILE[:SCALE]] [--sky-view] [--shaded] [--mixed 2|4] [--fog DENSITY] [--temporal N] [--probes D] [--present CURVE[:auto|:E][:bloom]] [--voxels LEVEL[:MODE]]... "
+                             "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] [--sky Z[:H[:G]]] [--env FILE[:SCALE]] [--sky-view] [--shaded] [--cutouts[=CUTOFF]] [--mixed 2|4] [--fog DENSITY] [--temporal N] [--probes D] [--present CURVE[:auto|:E][:bloom]] [--voxels LEVEL[:MODE]]... "
                              "[--dynamic FILE.obj [--dynamic-offset x,y,z]] "
                              "[--light dir:d:rgb | point:p:rgb:range | spot:p:d:rgb:range:inner:outer]...\n",
                      argv[0]);
@@ -419,6 +426,7 @@ int main(int argc, char** argv) {
     s.sky = sky;
     s.sky_view = sky_view;
     s.shaded = shaded;
+    s.cutout = cutout;
     s.has_env = has_env;
     s.env_texels = std::move(env_texels);
     s.env_size = env_size;

@@ -81,15 +81,39 @@ bool ConeTraceRenderer::rebuild_scene() {
     for (const Texture& t : model->textures) tex.push_back(vct_texture{t.rgba.data(), t.width, t.height});
     // the shading maps follow the diffuse ones in the one texture set (shaded)
     const int32_t shading_base = (int32_t)tex.size();
-    if (s_.shaded)
+    if (s_.shaded || s_.cutout > 0.0f)
         for (const Texture& t : model->shading_textures) tex.push_back(vct_texture{t.rgba.data(), t.width, t.height});
     if (!check(vct_set_textures(ctx_, tex.data(), (uint32_t)tex.size()), "vct_set_textures")) return false;
     const std::vector<int32_t> map = model->MaterialMap();
-    if (!check(vct_voxelize_textured(ctx_, v.data(), sizeof(Vertex), (uint32_t)v.size(), idx.data(),
-                                     (uint32_t)idx.size(), tri_mat.data(), kd4.data(), map.data(),
-                                     (uint32_t)(kd4.size() / 4), (uint32_t)offsetof(Vertex, TexCoords)),
-               "vct_voxelize_textured"))
+    // the cutout table (vct_host.h's rule): map_d, else the alpha of a four-channel map_Kd
+    std::vector<vct_cutout> cut;
+    bool masked = false;
+    if (s_.cutout > 0.0f)
+        for (const Material& mt : model->materials) {
+            vct_cutout c{-1, 0u, s_.cutout, 0u};
+            const int od = mt.shadingMaps[kMapOpacity], kd = mt.diffuseMaps.empty() ? -1 : mt.diffuseMaps[0];
+            if (od >= 0) {
+                c.map = shading_base + od;
+                c.channel = model->shading_textures[od].comp == 4 ? 3u : 0u;
+            } else if (kd >= 0 && model->textures[kd].comp == 4) {
+                c.map = kd;
+                c.channel = 3u;
+            }
+            masked |= c.map >= 0;
+            cut.push_back(c);
+        }
+    if (masked) {
+        if (!check(vct_voxelize_cutout(ctx_, v.data(), sizeof(Vertex), (uint32_t)v.size(), idx.data(), (uint32_t)idx.size(),
+                                       tri_mat.data(), kd4.data(), map.data(), cut.data(), (uint32_t)(kd4.size() / 4),
+                                       (uint32_t)offsetof(Vertex, TexCoords)),
+                   "vct_voxelize_cutout"))
+            return false;
+    } else if (!check(vct_voxelize_textured(ctx_, v.data(), sizeof(Vertex), (uint32_t)v.size(), idx.data(),
+                                            (uint32_t)idx.size(), tri_mat.data(), kd4.data(), map.data(),
+                                            (uint32_t)(kd4.size() / 4), (uint32_t)offsetof(Vertex, TexCoords)),
+                      "vct_voxelize_textured")) {
         return false;
+    }
     if (s_.shaded) {
         // Material::Ks, Ns as a roughness, the specular map, and as the normal map the slot the
         // reference reads (map_Kn) or else the height slot (nanosuit's *_ddn.png are normal maps)
@@ -219,8 +243,13 @@ void ConeTraceRenderer::Render() {
         std::swap(gb_[0], prev_gb_[0]);
         std::swap(gb_[1], prev_gb_[1]);
     }
-    if (s_.shaded) {
-        if (!ks_ && !check(vct_device_alloc(ctx_, (size_t)s_.width * s_.height * 16, &ks_), "alloc ks plane")) return;
+    if (s_.shaded && !ks_ && !check(vct_device_alloc(ctx_, (size_t)s_.width * s_.height * 16, &ks_), "alloc ks plane")) return;
+    if (vct_cutout_materials(ctx_) > 0) {   // a cutout mesh: the masked pass, flat or shaded records
+        if (!check(vct_gbuffer_cutout_device(ctx_, &vc, s_.width, s_.height, s_.roughness, (float*)gb_[0], (float*)gb_[1],
+                                             (float*)gb_[2], s_.shaded ? (float*)ks_ : nullptr, nullptr, nullptr, nullptr),
+                   "cutout G-buffer"))
+            return;
+    } else if (s_.shaded) {
         if (!check(vct_gbuffer_shaded_device(ctx_, &vc, s_.width, s_.height, s_.roughness, (float*)gb_[0], (float*)gb_[1],
                                              (float*)gb_[2], (float*)ks_, nullptr, nullptr, nullptr), "shaded G-buffer"))
             return;

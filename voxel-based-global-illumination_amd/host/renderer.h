@@ -75,6 +75,11 @@ struct ConeTraceSettings {
     // the shading G-buffer (include/vct_shading.h): vertex normals, normal and specular maps, Ks and
     // a roughness per material from the loader, and the specular plane tinted by Ks x map_Ks
     bool shaded = false;
+    // alpha cutouts (include/vct_cutout.h): > 0 = the cutoff.  A material with a map_d is cut by it
+    // (channel 3 of a four-channel file, else channel 0), one without by the alpha of a four-channel
+    // map_Kd (vct_host.h has the rule); the model goes through vct_voxelize_cutout and the frame
+    // through vct_gbuffer_cutout_device when a material is masked.  0: the mask is ignored
+    float cutout = 0.0f;
     // an environment map (include/vct_env.h): env_size^2 RGBA float texels, octahedral, uploaded
     // once with vct_set_env.  It takes the sky's place in every call above: vct_inject_env,
     // vct_env_cones_device and, with sky_view, vct_env_specular_device and

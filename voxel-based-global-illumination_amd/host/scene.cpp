@@ -161,6 +161,11 @@ void load_mtl(const std::string& path, std::vector<Material>& mats) {
             cur->diffuse_map = texture_name(rest_of_line(ss));
         } else if (cur && tag == "Ns") {
             read_floats(ss, &cur->Ns, 1);
+        } else if (cur && tag == "d") {
+            read_floats(ss, &cur->d, 1);
+        } else if (cur && tag == "map_d") {
+            // the opacity mask (include/vct_cutout.h): the same option skipping as the other maps
+            cur->shading_map[kMapOpacity] = texture_name(rest_of_line(ss));
         } else if (cur && (tag == "map_Ks" || tag == "map_Kn" || tag == "map_Bump" || tag == "map_bump" || tag == "bump")) {
             // the shading slots: map_Ks specular, map_Kn normal (aiTextureType_NORMALS in assimp
             // 3.3), map_Bump / map_bump / bump height; a later statement replaces the slot
@@ -541,11 +546,11 @@ bool Model::LoadObj(const std::string& path, std::string* err, bool load_texture
 }
 
 void Model::LoadShadingTextures() {
-    static const char* const kType[3] = {"texture_specular", "texture_normal", "texture_height"};
+    static const char* const kType[kMapSlots] = {"texture_specular", "texture_normal", "texture_height", "texture_opacity"};
     shading_textures.clear();
     shading_texture_errors.clear();
     for (Material& mt : materials)
-        for (int slot = 0; slot < 3; ++slot) {
+        for (int slot = 0; slot < kMapSlots; ++slot) {
             mt.shadingMaps[slot] = -1;
             const std::string& name = mt.shading_map[slot];
             if (name.empty()) continue;
@@ -564,6 +569,7 @@ void Model::LoadShadingTextures() {
                 t.path = name;
                 t.width = img.width;
                 t.height = img.height;
+                t.comp = img.comp;
                 shading_textures.push_back(std::move(t));
                 found = (int)shading_textures.size() - 1;
             }
@@ -591,6 +597,7 @@ void Model::LoadTextures() {
             t.path = mt.diffuse_map;
             t.width = img.width;
             t.height = img.height;
+            t.comp = img.comp;
             textures.push_back(std::move(t));
             found = (int)textures.size() - 1;
         }

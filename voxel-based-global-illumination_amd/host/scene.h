@@ -30,6 +30,7 @@ struct Texture {                   // stdafx.h:30-34 (GL id -> the decoded texel
     std::string type;              // "texture_diffuse" (model.cpp:58)
     std::string path;              // as written in the .mtl (the dedup key, model.cpp:160-166)
     uint32_t width = 0, height = 0;
+    int comp = 0;                  // the file's channel count before the expansion (stbi_load's comp)
     std::vector<uint8_t> rgba;     // RGBA8, row 0 = the image's top row (vct_texture)
 };
 
@@ -44,11 +45,13 @@ struct Material {                  // material.h:5-18
     // map_* path of the .mtl ("" = none) and its index in Model::shading_textures (-1: none,
     // or it failed to load).  map_Kn is assimp 3.3's aiTextureType_NORMALS, the slot the
     // reference reads; map_Bump / bump is the height slot, which it never reads
+    // map_d, the opacity mask, is a fourth slot (include/vct_cutout.h); d is the dissolve factor
     float Ns = 0.0f;
-    std::string shading_map[3];    // kMapSpecular, kMapNormal, kMapHeight
-    int shadingMaps[3] = {-1, -1, -1};
+    float d = 1.0f;
+    std::string shading_map[4];    // kMapSpecular, kMapNormal, kMapHeight, kMapOpacity
+    int shadingMaps[4] = {-1, -1, -1, -1};
 };
-enum { kMapSpecular = 0, kMapNormal = 1, kMapHeight = 2 };
+enum { kMapSpecular = 0, kMapNormal = 1, kMapHeight = 2, kMapOpacity = 3, kMapSlots = 4 };
 
 struct Mesh {                      // mesh.h:7-26 CPU copies (vertices, indices, material)
     std::vector<Vertex> vertices;

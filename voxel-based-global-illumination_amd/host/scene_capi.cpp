@@ -123,6 +123,32 @@ int vcth_shading_texture(const vcth_model* m, uint32_t i, const uint8_t** rgba8,
     return 0;
 }
 
+int vcth_material_opacity_map(const vcth_model* m, uint32_t i, const char** path, int32_t* texture) {
+    if (!m || i >= m->m.materials.size()) return -1;
+    const vcthost::Material& mt = m->m.materials[i];
+    if (path) *path = mt.shading_map[vcthost::kMapOpacity].c_str();
+    if (texture) *texture = mt.shadingMaps[vcthost::kMapOpacity];
+    return 0;
+}
+
+int vcth_material_dissolve(const vcth_model* m, uint32_t i, float* d) {
+    if (!m || i >= m->m.materials.size()) return -1;
+    if (d) *d = m->m.materials[i].d;
+    return 0;
+}
+
+int vcth_texture_channels(const vcth_model* m, uint32_t i, int* comp) {
+    if (!m || i >= m->m.textures.size()) return -1;
+    if (comp) *comp = m->m.textures[i].comp;
+    return 0;
+}
+
+int vcth_shading_texture_channels(const vcth_model* m, uint32_t i, int* comp) {
+    if (!m || i >= m->m.shading_textures.size()) return -1;
+    if (comp) *comp = m->m.shading_textures[i].comp;
+    return 0;
+}
+
 uint32_t vcth_num_shading_texture_errors(const vcth_model* m) {
     return m ? (uint32_t)m->m.shading_texture_errors.size() : 0u;
 }

@@ -36,6 +36,7 @@ from ._lib import VctCone, VctConeQueryArgs, VctProbeGrid
 from ._lib import VctVoxelPickArgs, VctVoxelViewArgs
 from ._lib import VctEnvSky
 from ._lib import VctShadingDesc, VctShadingMaterial
+from ._lib import VctCutout
 from ._lib import VctBloomParams, VctExposureParams, VctExposureState, VctPresentParams
 
 __all__ = ["VctShadingMaterial","VctEnvSky", "env_sky", "VctTemporalParams","Context", "VctError", "VctConfig", "VctCamera", "tiles_for_rank", "tile_offset", "VERTEX_FLOATS",
@@ -868,6 +869,92 @@ class Context:
                        *self._gbuf_ptrs(width, height, pos4, nrm4, alb4), self._dev(ks4, "ks4", _F32, 4 * n),
                        self._dev(geo4, "geo4", _F32, 4 * n), self._dev(tri_id, "tri_id", _I32, n),
                        self._dev(bary2, "bary2", _F32, 2 * n)), "gbuffer_shaded")
+
+    # -- alpha-cutout materials (include/vct_cutout.h) -----------------------
+    @staticmethod
+    def _cutout_table(cutouts):
+        """A (VctCutout array or None, entries) pair from None, VctCutout records, or
+        (map, channel, cutoff) tuples (vct.cutout.cutouts_from_model gives such a list)."""
+        if cutouts is None:
+            return None, 0
+        recs = []
+        for e in cutouts:
+            if not isinstance(e, VctCutout):
+                m, ch, cut = e
+                e = VctCutout(int(m), int(ch), float(cut), 0)
+            recs.append(e)
+        return (VctCutout * max(len(recs), 1))(*recs), len(recs)
+
+    def voxelize_cutout(self, verts, idx, tri_material=None, kd4=None, material_map=None, material_cutout=None,
+                        uv_offset=UV_OFFSET):
+        """vct_voxelize_cutout: voxelize(material_map=...) with a per-material cutout table
+        (VctCutout records or (map, channel, cutoff) tuples; None = every material opaque)."""
+        fn = _lib.bind_cutout_extension(self.lib, "vct_voxelize_cutout")
+        verts = np.ascontiguousarray(verts, dtype=np.float32)
+        assert verts.ndim == 2 and verts.shape[1] >= 3
+        idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+        mat = None if tri_material is None else np.ascontiguousarray(tri_material, dtype=np.uint32).reshape(-1)
+        kd = None if kd4 is None else np.ascontiguousarray(kd4, dtype=np.float32)
+        mm = None if material_map is None else np.ascontiguousarray(material_map, dtype=np.int32).reshape(-1)
+        if idx.size % 3:
+            raise VctError(_EINVAL, f"voxelize_cutout: {idx.size} indices, not a multiple of 3")
+        if mat is not None and mat.size != idx.size // 3:
+            raise VctError(_EINVAL, f"voxelize_cutout: tri_material has {mat.size} entries for {idx.size // 3} triangles")
+        if kd is not None and (kd.ndim != 2 or kd.shape[1] != 4):
+            raise VctError(_EINVAL, f"voxelize_cutout: kd4 must be [materials, 4], got {kd.shape}")
+        table, n_cut = self._cutout_table(material_cutout)
+        sizes = {n for n in (None if kd is None else kd.shape[0], None if mm is None else mm.size,
+                             None if table is None else n_cut) if n is not None}
+        if len(sizes) > 1:   # the C-ABI bounds kd4, the map and the table by one n_materials
+            raise VctError(_EINVAL, f"voxelize_cutout: kd4, material_map and material_cutout differ in length: {sorted(sizes)}")
+        n_mat = sizes.pop() if sizes else 0
+        st = fn(self.h, _fptr(verts), verts.shape[1] * 4, verts.shape[0], _fptr(idx), idx.size,
+                _fptr(mat) if mat is not None else None, _fptr(kd) if kd is not None else None,
+                _fptr(mm) if mm is not None else None, table, n_mat, uv_offset)
+        self._check(st, "voxelize_cutout")
+
+    def voxelize_cutout_device(self, verts, idx, tri_material=None, kd4=None, material_map=None, material_cutout=None,
+                               uv_offset=UV_OFFSET):
+        """vct_voxelize_cutout_device: voxelize_device's tensors; material_cutout stays a host
+        table (VctCutout records or (map, channel, cutoff) tuples; None = every material opaque)."""
+        fn = _lib.bind_cutout_extension(self.lib, "vct_voxelize_cutout_device")
+        if verts.dim() != 2 or verts.shape[1] < 3:
+            raise VctError(_EINVAL, f"voxelize_cutout_device: verts must be [V, F >= 3], got {tuple(verts.shape)}")
+        if str(idx.dtype) in _I64:
+            raise VctError(_EINVAL, "voxelize_cutout_device: idx must be int32 / uint32, not 64-bit")
+        n_idx = idx.numel()
+        if n_idx % 3:
+            raise VctError(_EINVAL, f"voxelize_cutout_device: {n_idx} indices, not a multiple of 3")
+        if kd4 is not None and (kd4.dim() != 2 or kd4.shape[1] != 4):
+            raise VctError(_EINVAL, f"voxelize_cutout_device: kd4 must be [materials, 4], got {tuple(kd4.shape)}")
+        table, n_cut = self._cutout_table(material_cutout)
+        sizes = {n for n in (None if kd4 is None else kd4.shape[0], None if material_map is None else material_map.numel(),
+                             None if table is None else n_cut) if n is not None}
+        if len(sizes) > 1:   # a longer map or table would let K1 read kd4 past its end on the device
+            raise VctError(_EINVAL, f"voxelize_cutout_device: kd4, material_map and material_cutout differ in length: "
+                                    f"{sorted(sizes)}")
+        n_mat = sizes.pop() if sizes else 0
+        st = fn(self.h, self._dev(verts, "verts"), verts.shape[1] * 4, verts.shape[0], self._dev(idx, "idx", _I32), n_idx,
+                self._dev(tri_material, "tri_material", _I32, n_idx // 3), self._dev(kd4, "kd4"),
+                self._dev(material_map, "material_map", ("torch.int32",), max(n_mat, 1)), table, n_mat, uv_offset)
+        self._check(st, "voxelize_cutout_device")
+
+    def gbuffer_cutout_device(self, cam, width, height, roughness, pos4, nrm4, alb4, ks4=None, geo4=None, tri_id=None,
+                              bary2=None):
+        """vct_gbuffer_cutout_device: the tile-binned pass over accepted candidates.  ks4 None: the
+        flat records of gbuffer_raster_device; else the shaded records of gbuffer_shaded_device
+        (needs a shading set), with its optional planes."""
+        fn = _lib.bind_cutout_extension(self.lib, "vct_gbuffer_cutout_device")
+        c = cam.to_ctypes() if hasattr(cam, "to_ctypes") else cam
+        n = width * height
+        self._check(fn(self.h, C.byref(c), width, height, float(roughness),
+                       *self._gbuf_ptrs(width, height, pos4, nrm4, alb4), self._dev(ks4, "ks4", _F32, 4 * n),
+                       self._dev(geo4, "geo4", _F32, 4 * n), self._dev(tri_id, "tri_id", _I32, n),
+                       self._dev(bary2, "bary2", _F32, 2 * n)), "gbuffer_cutout")
+
+    def cutout_materials(self) -> int:
+        """vct_cutout_materials: masked materials of the current mesh, 0 if none."""
+        return int(_lib.bind_cutout_extension(self.lib, "vct_cutout_materials")(self.h))
 
     def specular_tint_device(self, spec4, ks4, width, height, out4=None):
         """vct_specular_tint_device: out.rgb = spec.rgb * ks.rgb, out.a = spec.a (in place when

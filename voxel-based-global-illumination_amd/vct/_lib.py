@@ -98,6 +98,10 @@ SHADING_EXTENSIONS = ("vct_set_shading", "vct_gbuffer_shaded_device", "vct_specu
 VCT_SHADING_NO_ATTR = 0xFFFFFFFF
 VCT_SHADING_FLIP_GREEN = 1
 
+# include/vct_cutout.h: alpha-cutout materials, likewise HIP only (bind_cutout_extension)
+CUTOUT_EXTENSIONS = ("vct_voxelize_cutout", "vct_voxelize_cutout_device", "vct_gbuffer_cutout_device",
+                     "vct_cutout_materials")
+
 # include/vct_present.h: the HDR present, likewise HIP only (bind_present_extension)
 PRESENT_EXTENSIONS = ("vct_luminance_meter_device", "vct_exposure_update_device", "vct_bloom_scratch_bytes",
                       "vct_bloom_device", "vct_present_device")
@@ -337,6 +341,15 @@ class VctShadingDesc(C.Structure):      # vct_shading_desc
         ("bitangent_offset", C.c_uint32),
         ("materials", C.c_void_p),
         ("n_materials", C.c_uint32),
+    ]
+
+
+class VctCutout(C.Structure):           # vct_cutout, 16 bytes
+    _fields_ = [
+        ("map", C.c_int32),
+        ("channel", C.c_uint32),
+        ("cutoff", C.c_float),
+        ("reserved", C.c_uint32),
     ]
 
 
@@ -735,6 +748,28 @@ def bind_shading_extension(lib: C.CDLL, name: str):
     except AttributeError:
         raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
                              "(include/vct_shading.h is implemented by the HIP library only)") from None
+    fn.restype = res
+    fn.argtypes = args
+    return fn
+
+
+def bind_cutout_extension(lib: C.CDLL, name: str):
+    """The include/vct_cutout.h function `name` of `lib`, with its signature declared;
+    AttributeError (naming the library) if this implementation does not export it."""
+    P, u32, i32, f32 = C.c_void_p, C.c_uint32, C.c_int32, C.c_float
+    vox = (i32, [P, P, u32, u32, P, u32, P, P, P, C.POINTER(VctCutout), u32, u32])
+    sig = {
+        "vct_voxelize_cutout": vox,
+        "vct_voxelize_cutout_device": vox,
+        "vct_gbuffer_cutout_device": (i32, [P, C.POINTER(VctCamera), u32, u32, f32, P, P, P, P, P, P, P]),
+        "vct_cutout_materials": (u32, [P]),
+    }
+    res, args = sig[name]
+    try:
+        fn = getattr(lib, name)
+    except AttributeError:
+        raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
+                             "(include/vct_cutout.h is implemented by the HIP library only)") from None
     fn.restype = res
     fn.argtypes = args
     return fn

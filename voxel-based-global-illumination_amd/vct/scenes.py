@@ -170,6 +170,46 @@ def atrium() -> Scene:
     return s
 
 
+def cutout_masks(seed: int = 23):
+    """The generated masks of atrium_cutouts(), (H, W, 4) uint8 with the mask in every channel:
+    stripes (a lattice's bars), discs (a perforated sheet) and a noise mask with thin features."""
+    rgba = lambda a: np.ascontiguousarray(np.repeat(np.asarray(a, np.uint8)[..., None], 4, -1))
+    y, x = np.mgrid[0:32, 0:32]
+    stripes = rgba(np.where(((x % 8) < 3) | ((y % 8) < 3), 255, 0))                  # bars 3 of 8 texels wide, both ways
+    discs = rgba(np.where(((x % 16 - 7.5) ** 2 + (y % 16 - 7.5) ** 2) < 30.0, 0, 255))   # holes of radius ~5.5 in a 16 pitch
+    rng = np.random.default_rng(seed)
+    n = rng.random((64, 64))
+    n = (n + np.roll(n, 1, 0) + np.roll(n, 1, 1)) / 3.0                               # one-texel features, soft edges
+    noise = rgba(np.clip((n - 0.35) * 1200.0, 0, 255))
+    return [stripes, discs, noise]
+
+
+def atrium_cutouts(cutoff: float = 0.5):
+    """The atrium plus a masked part: a lattice screen under the roof opening, in front of the
+    light, and a few leaf cards in the court.  -> (scene, textures, cutouts): the masks of
+    cutout_masks() for vct_set_textures, and one (map, channel, cutoff) per material for
+    vct_voxelize_cutout (the atrium's own materials are opaque).  The scene has no diffuse maps."""
+    s = atrium()
+    s.name = "atrium_cutouts"
+    n_plain = len(s.kd)
+    lattice = s.material((0.35, 0.25, 0.15))
+    sheet = s.material((0.55, 0.55, 0.60))
+    leaf = s.material((0.25, 0.55, 0.20))
+    # the lattice: one quad across the roof opening, a little under the ceiling, 6 x 14 mask periods
+    s.quad((-0.36, 0.93, -0.86), (0.36, 0.93, -0.86), (0.36, 0.93, 0.86), (-0.36, 0.93, 0.86), (0, 1, 0), lattice,
+           uv=[(0, 0), (1.5, 0), (1.5, 3.5), (0, 3.5)])
+    # a perforated sheet between two ground-floor columns
+    s.quad((-0.5, -1.0, -0.3), (-0.5, 0.05, -0.3), (-0.5, 0.05, 0.2), (-0.5, -1.0, 0.2), (1, 0, 0), sheet,
+           uv=[(0, 0), (2, 0), (2, 1), (0, 1)])
+    # leaf cards: crossed quads over the fountain and two more in the court
+    for cx, cz, h0, r in ((0.0, 0.0, -0.8, 0.28), (0.3, 0.45, -1.0, 0.2), (-0.28, -0.5, -1.0, 0.22)):
+        for dx, dz in ((1.0, 0.0), (0.0, 1.0), (0.7071, 0.7071)):
+            a, b = (cx - r * dx, h0, cz - r * dz), (cx + r * dx, h0, cz + r * dz)
+            s.quad(a, b, (b[0], h0 + 2 * r, b[2]), (a[0], h0 + 2 * r, a[2]), (-dz, 0.0, dx), leaf)
+    table = [(-1, 0, float(cutoff))] * n_plain + [(0, 0, float(cutoff)), (1, 1, float(cutoff)), (2, 2, float(cutoff))]
+    return s, cutout_masks(), table
+
+
 def random_triangles(n_tri: int, seed: int = 7, size: float = 0.3) -> Scene:
     """Triangle soup inside [-1,1]^3 (sizes up to `size`), random materials."""
     rng = np.random.default_rng(seed)
