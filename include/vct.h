@@ -433,6 +433,7 @@ vct_status vct_dump_info(const char* stem, vct_config* cfg, uint32_t* what);
 #include "vct_emission.h"   /* emissive surfaces (additive; HIP library only) */
 #include "vct_sky.h"        /* sky light (additive; HIP library only) */
 #include "vct_dynamic.h"    /* dynamic layer (additive; HIP library only) */
+#include "vct_objects.h"    /* dynamic objects: device-posed instances (additive; HIP library only) */
 #include "vct_mixed.h"      /* mixed-resolution trace (additive; HIP library only) */
 #include "vct_fog.h"        /* volumetric fog (additive; HIP library only) */
 #include "vct_temporal.h"   /* temporal accumulation (additive; HIP library only) */

@@ -510,6 +510,53 @@
  *    emission and sky marks, the emission grid and the bounce source list; vct_inject_*
  *    and vct_build_mips (a full build) follow it as they follow vct_voxelize. */
 
+/* ---- dynamic objects (vct_objects_define / vct_objects_update*, include/vct_objects.h;
+ *      tests/objects_ref.py restates the transform rule, the feature's only new arithmetic) ----
+ *  The context holds at most one object set: n_objects rigid meshes O_0, O_1, ... in object
+ *    space, registered once, each with a pose P_k = (m[16], visible); every object starts
+ *    hidden.  The set sits on top of the static grid as the dynamic layer does, and excludes it.
+ *  The transform rule: T(O, P) is O with every vertex (x, y, z) replaced by
+ *        x' = ((m[0] x + m[4] y) + m[8]  z) + m[12]
+ *        y' = ((m[1] x + m[5] y) + m[9]  z) + m[13]
+ *        z' = ((m[2] x + m[6] y) + m[10] z) + m[14]
+ *    in float32, one rounding per operation, no fma contraction; m is column-major and m[3],
+ *    m[7], m[11], m[15] are not read.  Any matrix is legal: its contents are data, never a
+ *    status.  A non-finite result makes the triangle a skipped one under the K1 input rule.
+ *    Nothing is special-cased, so an identity matrix maps -0.0f to +0.0f (-0 + 0 = +0), and an
+ *    infinite coordinate stays in its own row and makes the vertex's other two coordinates NaN
+ *    (0 x inf).  T of a hidden object (visible == 0) is its
+ *    triangles with every vertex NaN: skipped by K1, zero triangles for the G-buffer passes.
+ *  Equality: let S be the static mesh and P_k the last pose given for object k.  After any
+ *    sequence of vct_objects_define / vct_objects_update* calls the context is, bit for bit,
+ *    the context after vct_voxelize(union(S, T(O_0, P_0), T(O_1, P_1), ...)), union being the
+ *    dynamic layer's concatenation extended to several meshes, in definition order, the set's
+ *    one material table behind S's.  Everything the layer's equality clause lists holds: K1's
+ *    sums and counts, albedo / occupancy and normals, the occupancy bits and the occupied set,
+ *    level 0 of every vct_inject_*, every mip face, K4, the marches, the bounce sources, every
+ *    composite, and both G-buffer passes in that triangle order.  It holds because an update
+ *    subtracts, modulo 2^64, exactly the terms the named objects' previous poses added, and
+ *    adds the new poses' terms; every other object's terms stay.  After vct_objects_define
+ *    the grid is S's; n_objects == 0 removes the set, and the grid is S's again.
+ *  A voxel only a moved or hidden object occupied: an all-zero record, albedo = normal =
+ *    (0,0,0,0), a +0 level-0 texel, a clear occupancy bit, absent from the occupied list.
+ *  Materials: Kd only, one table for the set, under the K1 input rule; the set's triangles
+ *    shade flat and are opaque.  A live shading set and cutout table describe S's triangles and
+ *    are carried over every update.
+ *  Packed sums: the layer's rule, with max|value| the larger of the static pass's and the
+ *    running maximum over everything the set ever added (conservative; the sums are the same
+ *    either way).  When the conversion is needed after a subset moved, what that update added
+ *    is retracted, the occupied records are converted, and the same terms are added again in
+ *    the one-sum-per-word form.
+ *  State: before a successful vct_voxelize* / vct_load_grid every call is VCT_ESTATE.  A new
+ *    vct_voxelize* / vct_load_grid drops the set; what it leaves is the static grid, and an
+ *    update is VCT_ESTATE until the set is defined again.  vct_objects_define with a layer in
+ *    place and vct_voxelize_dynamic* with a set defined are VCT_ESTATE; either is removed by its
+ *    own empty call.  vct_save_grid with a set saves the union as a plain grid.
+ *  Errors are found on the host before any launch (include/vct_objects.h lists them): the
+ *    context, the set and the marks stay exactly as they were.
+ *  An update of n > 0 objects invalidates what vct_voxelize_dynamic invalidates; n == 0
+ *    touches nothing. */
+
 /* ---- mixed-resolution trace (include/vct_mixed.h; tests/mixed_ref.py restates it) ----
  *  All arithmetic is float32, one rounding per operation, no fma contraction; integers are
  *    exact.  K4 is a function of a pixel's G-buffer record (ray order and tile layout change

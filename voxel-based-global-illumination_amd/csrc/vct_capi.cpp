@@ -332,6 +332,7 @@ void vct_destroy(vct_ctx* c) {
     bounce_free(c);
     emission_free(c);
     dynamic_free(c);
+    objects_free(c);
     fog_free(c);
     env_free(c);
     shading_free(c);

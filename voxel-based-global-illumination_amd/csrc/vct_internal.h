@@ -130,6 +130,36 @@ struct Dynamic {
     void* h_head = nullptr;               // pinned host copy of an update's read-back (counts, error word)
 };
 
+// The object set (vct_objects.hip; vct_spec.h "dynamic objects").  Rigid meshes registered once
+// in object space and placed by a matrix per object; an update retracts and re-adds the records
+// of the objects it names and of no other.  Per triangle of the set the context keeps K1's setup
+// record for the pose in place (TriGeom, the six 16.16 values, the candidate count: 120 bytes),
+// so a retraction needs neither the old pose nor the mesh.  Object k's triangles are
+// [first[k], first[k + 1]) of the set and sit behind the static ones in Mesh::tri.  Like the
+// layer's, the records belong to the grid of epoch `epoch`: an update carries them to the epoch
+// it makes, any other voxelization or load drops them.
+struct Objects {
+    bool live = false;                    // a set is defined ...
+    uint32_t epoch = 0;                   // ... for the grid of this vct_ctx::grid_epoch
+    uint32_t n_static = 0;                // triangles of Mesh::tri that are the static scene's
+    uint32_t n_objects = 0, n_tri = 0, n_visible = 0;
+    uint32_t maxabs = 0;                  // largest |16.16 value| the set ever added (the packed-sum rule)
+    std::vector<uint32_t> first;          // [n_objects + 1] triangle range of each object
+    float* pos = nullptr;                 // packed object-space positions, 3 floats a vertex (device)
+    uint32_t* idx = nullptr;              // [3 n_tri] indices into pos
+    uint32_t* mat = nullptr;              // [n_tri] material ids
+    float4* kd = nullptr;                 // [n_mat] the set's table (nullptr: albedo 1)
+    uint32_t n_mat = 0;
+    void* rec = nullptr;                  // geom | fix | counts of n_tri triangles, then the head (device)
+    uint32_t* vis = nullptr;              // [n_objects] 1 = visible
+    unsigned long long* mask = nullptr;   // [n^3 / 64] voxels an update hit; all zero between updates
+    void* tab = nullptr;                  // an update's table: prefix, first triangle and id per named object,
+    void* h_tab = nullptr;                // then the poses (device; pinned host staging of the same layout)
+    void* h_head = nullptr;               // pinned host copy of an update's read-back
+    uint32_t last_moved = 0, last_touched = 0;
+    unsigned long long last_cand = 0;
+};
+
 struct Mesh {
     float4* tri = nullptr;        // [n_tri][4] : v0, e1 = v1-v0, e2 = v2-v0, (kd rgb, diffuse map as int bits; -1 none)
     float4* uv = nullptr;         // [n_tri][2] : (u0 v0 u1 v1), (u2 v2 0 0)  (textured voxelizations)
@@ -374,6 +404,7 @@ struct vct_ctx {
     vct::Bounce bounce;                 // source list of vct_inject_bounces
     vct::Emission em;                   // emission grid of vct_voxelize_emission*
     vct::Dynamic dyn;                   // dynamic layer of vct_voxelize_dynamic*
+    vct::Objects obj;                   // object set of vct_objects_define
     vct::Fog fog;                       // scatter volume of vct_build_fog
     vct::Env env;                       // map and mips of vct_set_env
     vct::Shading shade;                 // attribute records and materials of vct_set_shading
@@ -571,6 +602,15 @@ void emission_free(vct_ctx* c);
 // release with the context
 inline bool dynamic_live(const vct_ctx* c) { return c->dyn.live && c->dyn.epoch == c->grid_epoch; }
 void dynamic_free(vct_ctx* c);
+// object set (vct_objects.hip): the context holds a set for the current grid; release with the
+// context.  The set and the layer exclude each other (a layer in place: one with triangles)
+inline bool objects_live(const vct_ctx* c) { return c->obj.live && c->obj.epoch == c->grid_epoch; }
+inline bool layer_in_place(const vct_ctx* c) { return dynamic_live(c) && c->dyn.layer[c->dyn.cur].n_tri > 0; }
+void objects_free(vct_ctx* c);
+// the triangles of Mesh::tri that the last vct_voxelize* put there
+inline uint32_t static_triangles(const vct_ctx* c) {
+    return objects_live(c) ? c->obj.n_static : dynamic_live(c) ? c->dyn.n_static : c->mesh.n_tri;
+}
 // volumetric fog (vct_fog.hip): the context's scatter volume was built from the current pyramid;
 // release with the context
 inline bool fog_current(const vct_ctx* c) {

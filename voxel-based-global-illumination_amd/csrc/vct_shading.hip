@@ -150,7 +150,7 @@ extern "C" vct_status vct_set_shading(vct_ctx* c, const vct_shading_desc* d) {
     if (!c->grid.voxelized || !c->mesh.tri) return lfail(c, VCT_ESTATE, "set_shading before voxelize");
     if (!d->verts || !d->idx || !d->materials || d->n_materials == 0)
         return lfail(c, VCT_EINVAL, "set_shading: NULL verts, idx or materials, or n_materials == 0");
-    const uint32_t n_static = dynamic_live(c) ? c->dyn.n_static : c->mesh.n_tri;
+    const uint32_t n_static = static_triangles(c);
     if (d->n_idx % 3 != 0 || d->n_idx / 3 != n_static)
         return lfail(c, VCT_EINVAL, "set_shading: n_idx = " + std::to_string(d->n_idx) + ", the static voxelization has " +
                                         std::to_string(n_static) + " triangles");

@@ -8,6 +8,7 @@
 //                [--light SPEC]... [--shadow-tan T] [--sky Z[:H[:G]]] [--env FILE[:SCALE]] [--sky-view] [--mixed 2|4]
 //                [--fog DENSITY] [--temporal N] [--probes D] [--present CURVE[:auto|:E][:bloom]]
 //                [--dynamic FILE.obj [--dynamic-offset x,y,z]]
+//                [--object FILE.obj[@x,y,z]]...
 //                [--voxels LEVEL[:MODE]]...
 //   (devices > 1: one process drives that many GPUs through vct_create_multi)
 //   --model: the model matrix of the reference's draw, T(0,-1.75,0) S(0.2)
@@ -65,6 +66,11 @@
 //            on top of the first one's grid; Kd materials only (its diffuse maps are not loaded).
 //            --dynamic-offset: a world-space translation applied after the model matrix of
 //            --model (default 0,0,0).  The grid is fitted to the first model alone;
+//   --object: a further model as one rigid object of the context's object set
+//            (include/vct_objects.h), repeatable, in set order; @x,y,z: a world-space translation
+//            applied after the model matrix of --model.  The set is registered once in object
+//            space and the device applies each matrix; Kd materials only.  Exclusive with
+//            --dynamic;
 //   --light:  one light of a light list (include/vct_lights.h), repeatable, in list order; with
 //            any --light the list replaces the default directional light.  SPEC is colon-
 //            separated fields of comma-separated floats, world units, angles in degrees:
@@ -283,6 +289,8 @@ int main(int argc, char** argv) {
     std::string dynamic;
     bool has_dynamic = false, has_offset = false;
     float dyn_offset[3] = {0.0f, 0.0f, 0.0f};
+    struct ObjectArg { std::string file; float offset[3]; };
+    std::vector<ObjectArg> objects;
     bool ref_model = true, fit_grid = true;
     int bounces = 0;
     std::string linear;
@@ -396,6 +404,16 @@ int main(int argc, char** argv) {
             if (dynamic.empty() || dynamic.rfind("--", 0) == 0) { std::fprintf(stderr, "--dynamic needs a file (--dynamic FILE.obj)\n"); return 2; }
             has_dynamic = true;
         }
+        else if (a == "--object" || a.rfind("--object=", 0) == 0) {
+            const std::string spec = a == "--object" ? (i + 1 < argc ? argv[++i] : "") : a.substr(9);
+            ObjectArg o{spec.substr(0, spec.rfind('@')), {0.0f, 0.0f, 0.0f}};
+            if (o.file.empty() || o.file.rfind("--", 0) == 0) { std::fprintf(stderr, "--object needs a file (--object FILE.obj[@x,y,z])\n"); return 2; }
+            if (spec.rfind('@') != std::string::npos && !parse_offset(spec.substr(spec.rfind('@') + 1), o.offset)) {
+                std::fprintf(stderr, "malformed --object offset %s\n", spec.c_str());
+                return 2;
+            }
+            objects.push_back(o);
+        }
         else if (a.rfind("--", 0) == 0) { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
         else pos.push_back(a);
     }
@@ -403,7 +421,7 @@ int main(int argc, char** argv) {
     if (pos.empty()) {
         std::fprintf(stderr, "usage: %s model.obj [grid] [width] [height] [frames] [out.ppm] [devices] "
                              "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] [--sky Z[:H[:G]]] [--env FILE[:SCALE]] [--sky-view] [--shaded] [--cutouts[=CUTOFF]] [--mixed 2|4] [--fog DENSITY] [--temporal N] [--probes D] [--present CURVE[:auto|:E][:bloom]] [--voxels LEVEL[:MODE]]... "
-                             "[--dynamic FILE.obj [--dynamic-offset x,y,z]] "
+                             "[--dynamic FILE.obj [--dynamic-offset x,y,z]] [--object FILE.obj[@x,y,z]]... "
                              "[--light dir:d:rgb | point:p:rgb:range | spot:p:d:rgb:range:inner:outer]...\n",
                      argv[0]);
         return 2;
@@ -419,6 +437,7 @@ int main(int argc, char** argv) {
     if (bounces < 0) { std::fprintf(stderr, "--bounces must be >= 0\n"); return 2; }
     if (!(shadow_tan >= 0.0f) || !std::isfinite(shadow_tan)) { std::fprintf(stderr, "--shadow-tan must be finite and >= 0\n"); return 2; }
     if (has_offset && !has_dynamic) { std::fprintf(stderr, "--dynamic-offset needs --dynamic FILE.obj\n"); return 2; }
+    if (has_dynamic && !objects.empty()) { std::fprintf(stderr, "--object and --dynamic exclude each other\n"); return 2; }
     s.bounces = (uint32_t)bounces;
     s.shadow_tan = shadow_tan;
     s.lights = lights;
@@ -475,6 +494,19 @@ int main(int argc, char** argv) {
         s.dynamic_model = "dynamic";
         for (int i = 0; i < 16; ++i) s.dynamic_matrix[i] = s.model[i];
         for (int k = 0; k < 3; ++k) s.dynamic_matrix[12 + k] = s.model[12 + k] + dyn_offset[k];
+    }
+    for (size_t k = 0; k < objects.size(); ++k) {   // rigid objects: the same model matrix, then each one's offset
+        auto obj = std::make_shared<Model>();
+        if (!obj->LoadObj(objects[k].file, &err, false)) {
+            std::fprintf(stderr, "ERROR::OBJ:: %s\n", err.c_str());
+            return 1;
+        }
+        ConeTraceSettings::Object o;
+        o.model = "object" + std::to_string(k);
+        A.models[o.model] = obj;
+        for (int i = 0; i < 16; ++i) o.matrix[i] = s.model[i];
+        for (int j = 0; j < 3; ++j) o.matrix[12 + j] = s.model[12 + j] + objects[k].offset[j];
+        s.objects.push_back(o);
     }
     auto r = std::make_shared<ConeTraceRenderer>("test", s);
     A.renderers["ConeTrace"] = r;

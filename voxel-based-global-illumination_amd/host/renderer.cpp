@@ -139,6 +139,56 @@ bool ConeTraceRenderer::rebuild_scene() {
     scene_dirty_ = false;
     dynamic_dirty_ = true;              // a voxelization drops the layer: put it back before the light
     if (!s_.dynamic_model.empty()) return update_dynamic();
+    if (!s_.objects.empty()) return define_objects();   // a voxelization drops the set too
+    return relight();
+}
+
+void ConeTraceRenderer::SetObjectMatrix(size_t i, const float m[16]) {
+    if (i >= s_.objects.size() || std::memcmp(s_.objects[i].matrix, m, sizeof s_.objects[i].matrix) == 0) return;
+    std::memcpy(s_.objects[i].matrix, m, sizeof s_.objects[i].matrix);
+    object_dirty_.resize(s_.objects.size(), 1);
+    object_dirty_[i] = 1;
+}
+
+bool ConeTraceRenderer::define_objects() {
+    // every model in object space, as the loader gives it; one material table for the set: the
+    // models' tables back to back
+    const size_t n = s_.objects.size();
+    std::vector<std::vector<Vertex>> v(n);
+    std::vector<std::vector<unsigned>> idx(n), tri_mat(n);
+    std::vector<float> kd4;
+    std::vector<vct_object_mesh> meshes(n);
+    for (size_t k = 0; k < n; ++k) {
+        auto model = AssetsManager::Instance().models[s_.objects[k].model];
+        if (!model) { error_ = "no model '" + s_.objects[k].model + "'"; status_ = VCT_EINVAL; return false; }
+        std::vector<float> kd;
+        model->Flatten(v[k], idx[k], tri_mat[k], kd);
+        for (unsigned& m : tri_mat[k]) m += (unsigned)(kd4.size() / 4);
+        kd4.insert(kd4.end(), kd.begin(), kd.end());
+        meshes[k].verts = v[k].data(); meshes[k].vertex_stride = sizeof(Vertex); meshes[k].n_verts = (uint32_t)v[k].size();
+        meshes[k].idx = idx[k].data(); meshes[k].n_idx = (uint32_t)idx[k].size();
+        meshes[k].tri_material = tri_mat[k].data();
+    }
+    if (!check(vct_objects_define(ctx_, meshes.data(), (uint32_t)n, kd4.empty() ? nullptr : kd4.data(), (uint32_t)(kd4.size() / 4)),
+               "vct_objects_define"))
+        return false;
+    object_dirty_.assign(n, 1);
+    return update_objects();
+}
+
+bool ConeTraceRenderer::update_objects() {
+    std::vector<uint32_t> ids;
+    std::vector<vct_object_pose> poses;
+    for (size_t k = 0; k < s_.objects.size(); ++k) {
+        if (!object_dirty_[k]) continue;
+        vct_object_pose p{};
+        std::memcpy(p.m, s_.objects[k].matrix, sizeof p.m);
+        p.visible = 1;
+        ids.push_back((uint32_t)k);
+        poses.push_back(p);
+    }
+    if (!check(vct_objects_update(ctx_, ids.data(), poses.data(), (uint32_t)ids.size()), "vct_objects_update")) return false;
+    object_dirty_.assign(s_.objects.size(), 0);
     return relight();
 }
 
@@ -233,6 +283,8 @@ void ConeTraceRenderer::Render() {
     if (scene_dirty_) {
         if (!rebuild_scene()) return;
     } else if (!s_.dynamic_model.empty() && dynamic_dirty_ && !update_dynamic()) {
+        return;
+    } else if (std::find(object_dirty_.begin(), object_dirty_.end(), 1) != object_dirty_.end() && !update_objects()) {
         return;
     }
     auto cam = AssetsManager::Instance().ActiveCamera();

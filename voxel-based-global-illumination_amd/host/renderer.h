@@ -107,6 +107,16 @@ struct ConeTraceSettings {
     // inject and the mips, not K1 over the static scene.  Its materials are Kd only
     std::string dynamic_model;
     float dynamic_matrix[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    // rigid objects (include/vct_objects.h): registry names of further models, each with its
+    // own model matrix.  They are registered once after a voxelization, in object space; a
+    // frame then pays vct_objects_update for the objects whose matrix changed
+    // (SetObjectMatrix), the inject and the mips.  The device applies the matrix.  Kd materials
+    // only; exclusive with dynamic_model
+    struct Object {
+        std::string model;
+        float matrix[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    };
+    std::vector<Object> objects;
 };
 
 class ConeTraceRenderer : public Renderer {
@@ -118,6 +128,8 @@ public:
     void MarkSceneDirty() { scene_dirty_ = true; }
     // move the dynamic object: the next Render() replaces the layer and relights
     void SetDynamicMatrix(const float m[16]);
+    // move object i of ConeTraceSettings::objects: the next Render() updates it alone and relights
+    void SetObjectMatrix(size_t i, const float m[16]);
     bool ok() const { return status_ == VCT_OK; }
     const std::string& error() const { return error_; }
     double last_trace_ms() const { return last_ms_; }
@@ -136,6 +148,8 @@ private:
     bool check(vct_status s, const char* what);
     bool rebuild_scene();
     bool update_dynamic();                // the dynamic model, placed by its matrix, as the context's layer
+    bool define_objects();                // the settings' objects as the context's set, all placed
+    bool update_objects();                // vct_objects_update of the objects whose matrix changed
     bool relight();                       // inject -> mips (-> sky, bounces), as after every voxelization
     // row f3 into `lin` (float4) or `rgba` (packed 8-bit), with the light list when there is one
     vct_status composite(float* lin, uint32_t* rgba);
@@ -174,6 +188,7 @@ private:
     int hist_cur_ = 0;
     bool scene_dirty_ = true;
     bool dynamic_dirty_ = true;           // the dynamic matrix changed since the layer was voxelized
+    std::vector<char> object_dirty_;      // per object: its matrix changed since the last update
     vct_status status_ = VCT_OK;
     std::string error_;
     double last_ms_ = 0.0;

@@ -1247,6 +1247,68 @@ class Context:
         self._check(fn(self.h, C.byref(n)), "dynamic_voxels")
         return int(n.value)
 
+    # -- dynamic objects (include/vct_objects.h) ------------------------------
+    def objects_define(self, meshes, kd4: np.ndarray | None = None):
+        """vct_objects_define: register the set.  meshes: a sequence of (verts [V, F >= 3]
+        float32 in object space, idx [3T], tri_material [T] or None); kd4: the set's one material
+        table [M, 4] or None (albedo 1).  Every object starts hidden; an empty sequence removes
+        the set."""
+        fn = _lib.bind_objects_extension(self.lib, "vct_objects_define")
+        kd = None if kd4 is None else np.ascontiguousarray(kd4, dtype=np.float32)
+        if kd is not None and (kd.ndim != 2 or kd.shape[1] != 4):
+            raise VctError(_EINVAL, f"objects_define: kd4 must be [materials, 4], got {kd.shape}")
+        keep, arr = [], (_lib.VctObjectMesh * max(len(meshes), 1))()
+        for k, mesh in enumerate(meshes):
+            verts, idx = mesh[0], mesh[1]
+            mat = mesh[2] if len(mesh) > 2 else None
+            verts = np.ascontiguousarray(verts, dtype=np.float32)
+            if verts.ndim != 2 or verts.shape[1] < 3:
+                raise VctError(_EINVAL, f"objects_define: object {k}: verts must be [V, F >= 3], got {verts.shape}")
+            idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+            mat = None if mat is None else np.ascontiguousarray(mat, dtype=np.uint32).reshape(-1)
+            if mat is not None and mat.size != idx.size // 3:
+                raise VctError(_EINVAL, f"objects_define: object {k}: tri_material has {mat.size} entries for "
+                                        f"{idx.size // 3} triangles")
+            keep.append((verts, idx, mat))
+            arr[k].verts, arr[k].vertex_stride, arr[k].n_verts = verts.ctypes.data, verts.shape[1] * 4, verts.shape[0]
+            arr[k].idx, arr[k].n_idx = idx.ctypes.data, idx.size
+            arr[k].tri_material = mat.ctypes.data if mat is not None else None
+        self._check(fn(self.h, arr, len(meshes), _fptr(kd) if kd is not None else None,
+                       0 if kd is None else kd.shape[0]), "objects_define")
+
+    def objects_update(self, ids, poses: np.ndarray):
+        """vct_objects_update: place the objects `ids` by `poses`, host arrays: poses is n records
+        of 80 bytes (vct.objects.POSE, or any contiguous array of 80 n bytes)."""
+        fn = _lib.bind_objects_extension(self.lib, "vct_objects_update")
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        poses = np.ascontiguousarray(poses)
+        if poses.nbytes != 80 * ids.size:
+            raise VctError(_EINVAL, f"objects_update: {poses.nbytes} bytes of poses for {ids.size} ids (80 each)")
+        self._check(fn(self.h, _fptr(ids), _fptr(poses), ids.size), "objects_update")
+
+    def objects_update_device(self, ids, poses):
+        """vct_objects_update_device: ids a host array, poses a torch tensor on the context's
+        device: [n, 20] float32 (the last four columns hold the bits of visible and reserved) or
+        [n, 80] uint8."""
+        fn = _lib.bind_objects_extension(self.lib, "vct_objects_update_device")
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        if poses is not None and not isinstance(poses, int):
+            per = {"torch.float32": 20, "torch.uint8": 80}.get(str(poses.dtype))
+            if per is None or poses.dim() != 2 or poses.shape[1] != per:
+                raise VctError(_EINVAL, "objects_update_device: poses must be [n, 20] float32 or [n, 80] uint8, got "
+                                        f"{tuple(poses.shape)} {poses.dtype}")
+            if poses.shape[0] < ids.size:
+                raise VctError(_EINVAL, f"objects_update_device: {poses.shape[0]} poses for {ids.size} ids")
+        self._check(fn(self.h, _fptr(ids), self._dev(poses, "poses", ("torch.float32", "torch.uint8")), ids.size),
+                    "objects_update_device")
+
+    def objects_stats(self) -> dict:
+        """vct_objects_get_stats as a dict (all zero without a set); never waits."""
+        fn = _lib.bind_objects_extension(self.lib, "vct_objects_get_stats")
+        st = _lib.VctObjectsStats()
+        self._check(fn(self.h, C.byref(st)), "objects_stats")
+        return {k: int(getattr(st, k)) for k, _ in _lib.VctObjectsStats._fields_ if k != "reserved"}
+
     # -- grid access ------------------------------------------------------
     def download_level(self, level: int, face: int = 0) -> np.ndarray:
         nl, _ = self.level_dims(level)

@@ -53,6 +53,10 @@ SKY_EXTENSIONS = ("vct_sky_cones_device", "vct_inject_sky")
 # include/vct_dynamic.h: the dynamic layer, likewise HIP only (bind_dynamic_extension)
 DYNAMIC_EXTENSIONS = ("vct_voxelize_dynamic", "vct_voxelize_dynamic_device", "vct_dynamic_voxels")
 
+# include/vct_objects.h: dynamic objects, likewise HIP only (bind_objects_extension)
+OBJECTS_EXTENSIONS = ("vct_objects_define", "vct_objects_update", "vct_objects_update_device", "vct_objects_get_stats")
+VCT_MAX_OBJECTS = 4096
+
 # include/vct_mixed.h: the mixed-resolution trace, likewise HIP only (bind_mixed_extension)
 MIXED_EXTENSIONS = ("vct_mixed_default_params", "vct_trace_cones_device", "vct_mixed_pick_device",
                     "vct_mixed_upsample_device", "vct_mixed_scatter_device", "vct_trace_mixed_device")
@@ -822,6 +826,54 @@ def bind_dynamic_extension(lib: C.CDLL, name: str):
     except AttributeError:
         raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
                              "(include/vct_dynamic.h is implemented by the HIP library only)") from None
+    fn.restype = res
+    fn.argtypes = args
+    return fn
+
+
+class VctObjectMesh(C.Structure):     # vct_object_mesh: host arrays
+    _fields_ = [
+        ("verts", C.c_void_p),
+        ("vertex_stride", C.c_uint32),
+        ("n_verts", C.c_uint32),
+        ("idx", C.c_void_p),
+        ("n_idx", C.c_uint32),
+        ("tri_material", C.c_void_p),
+    ]
+
+
+class VctObjectPose(C.Structure):     # vct_object_pose, 80 bytes
+    _fields_ = [("m", C.c_float * 16), ("visible", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class VctObjectsStats(C.Structure):   # vct_objects_stats, 32 bytes
+    _fields_ = [
+        ("n_objects", C.c_uint32),
+        ("n_triangles", C.c_uint32),
+        ("n_visible", C.c_uint32),
+        ("last_moved_triangles", C.c_uint32),
+        ("last_candidates", C.c_uint64),
+        ("last_touched_voxels", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+def bind_objects_extension(lib: C.CDLL, name: str):
+    """The include/vct_objects.h function `name` of `lib`, with its signature declared;
+    AttributeError (naming the library) if this implementation does not export it."""
+    P, u32, i32 = C.c_void_p, C.c_uint32, C.c_int32
+    sig = {
+        "vct_objects_define": (i32, [P, C.POINTER(VctObjectMesh), u32, P, u32]),
+        "vct_objects_update": (i32, [P, P, P, u32]),
+        "vct_objects_update_device": (i32, [P, P, P, u32]),
+        "vct_objects_get_stats": (i32, [P, C.POINTER(VctObjectsStats)]),
+    }
+    res, args = sig[name]
+    try:
+        fn = getattr(lib, name)
+    except AttributeError:
+        raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
+                             "(include/vct_objects.h is implemented by the HIP library only)") from None
     fn.restype = res
     fn.argtypes = args
     return fn
