@@ -444,5 +444,6 @@ vct_status vct_dump_info(const char* stem, vct_config* cfg, uint32_t* what);
 #include "vct_shading.h"    /* the shading G-buffer: smooth normals, maps, per-material Ks (additive; HIP library only) */
 #include "vct_present.h"    /* the HDR present: meter, auto-exposure, bloom, tone curves (additive; HIP library only) */
 #include "vct_cutout.h"     /* alpha-cutout materials: masked K1 and a masked G-buffer pass (additive; HIP library only) */
+#include "vct_motion.h"     /* object motion: the previous-position plane from the set's poses (additive; HIP library only) */
 
 #endif /* VCT_H */

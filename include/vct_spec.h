@@ -1112,4 +1112,51 @@
  *    (k, t).  A mask index >= the CURRENT texture count (a later, smaller vct_set_textures) is no
  *    mask: the shading rule for a stale map.  Dynamic-layer triangles are opaque.
  *  No new literal. */
+
+/* ---- object motion (vct_objects_poses_device / vct_objects_motion_device, include/vct_motion.h;
+ * tests/motion_ref.py restates it) ------------------------------------------------------------------
+ *  The set remembers, per object, the last pose an update gave it, all 20 words as given (the
+ *    device form's visible and reserved words included); all zero before the first one, so a
+ *    never-posed object has visible == 0.  vct_objects_poses_device copies these n_objects records.
+ *  Input rule, vct_objects_motion_device (host memory, checked before any launch; nothing is
+ *    written).  VCT_EINVAL: NULL pos4, tri_id, bary2, prev_poses or motion4; pos4, nrm4, motion4,
+ *    prev_nrm4 or prev_poses not 16-byte aligned, bary2 not 8-byte, tri_id or stats not 4-byte;
+ *    width or height 0, above 65536, or more than 2^31 - 1 pixels (the temporal call's limits);
+ *    exactly one of nrm4 and prev_nrm4 given; n_prev != the set's n_objects (tested after the
+ *    state).  VCT_ESTATE: no set is defined.  Pixel contents, ids, barycentrics and matrix contents
+ *    are data, never a status.
+ *  The pixel.  float32, one rounding per operation, fmaf only where written; dot3 and unit() are
+ *    those of "shading attributes", the transform rule that of "dynamic objects".  n_static = the
+ *    static triangles, n_set = the set's, first[o] = object o's first triangle within the set,
+ *    k = tri_id, (b1, b2) = bary2, cur[o] = the set's pose of object o, prev = prev_poses.
+ *    1. pos4.w == 0: motion4 = prev_nrm4 = +0; the pixel is in no count.
+ *    2. k >= n_static + n_set (0xFFFFFFFF included): motion4 = 0, prev_nrm4 = nrm4; APPEARED.
+ *    3. k < n_static: the static record, motion4 = (pos4.xyz, 1.0f), prev_nrm4 = nrm4, bit for bit;
+ *       STILL.
+ *    4. Otherwise o = the last object with first[o] <= k - n_static (an object without triangles
+ *       is never the last one), and
+ *       a. prev[o].visible == 0: motion4 = 0, prev_nrm4 = nrm4; APPEARED.
+ *       b. m[j] of cur[o] and prev[o] have the same bits for the twelve j the transform rule reads
+ *          (j % 4 != 3; so -0.0f differs from +0.0f, and a NaN equals itself): the static record;
+ *          STILL.  cur[o].visible is not read: no pass writes the id of a hidden object's triangle.
+ *       c. Else, with v_i the triangle's object-space vertices (i = 0, 1, 2, in index order),
+ *          p_i = the transform rule on v_i with prev[o].m, c_i = the same with cur[o].m:
+ *            q = fmaf(b2, p_2 - p_0, fmaf(b1, p_1 - p_0, p_0))    per component ("diffuse maps" form)
+ *          motion4 = (q, 1.0f), MOVED, where the three components of q are finite; else
+ *          motion4 = 0, APPEARED.
+ *          face(a) = e1 x e2 with e1 = a_1 - a_0, e2 = a_2 - a_0 and the cross product of
+ *          "shading attributes" step 2 (x = e1.y e2.z - e1.z e2.y, ...): n' = unit(face(p)),
+ *          n = unit(face(c)).  Where both are defined, prev_nrm4 = (n', 0), negated when
+ *          dot3(n, nrm4.xyz) < 0 (the pass had flipped the face normal towards the viewer; a NaN
+ *          compares false); where either is not, prev_nrm4 = nrm4.  prev_nrm4 does not depend on
+ *          whether q is finite.
+ *  stats = {valid, STILL, MOVED, APPEARED} over the frame, valid = the sum of the other three;
+ *    written, not accumulated.
+ *  Consequences.  With no object moved since the snapshot every valid pixel has the static record,
+ *    and vct_temporal_accumulate_device gives with that motion4 what it gives with motion4 == NULL,
+ *    in every bit.  For a rigid motion q is the point the pixel's surface point was at, and n' the
+ *    normal it had: with prev_nrm4 as the accumulate's nrm4 its normal test compares last frame's
+ *    normal with last frame's G-buffer and its plane test measures along that normal, whatever
+ *    the rotation.
+ *  No new literal. */
 #endif /* VCT_SPEC_H */

@@ -152,6 +152,8 @@ struct Objects {
     uint32_t n_mat = 0;
     void* rec = nullptr;                  // geom | fix | counts of n_tri triangles, then the head (device)
     uint32_t* vis = nullptr;              // [n_objects] 1 = visible
+    void* poses = nullptr;                // [n_objects] vct_object_pose: the last pose given to each, all zero before
+    uint32_t* d_first = nullptr;          // [n_objects + 1] `first` on the device (vct_motion.hip)
     unsigned long long* mask = nullptr;   // [n^3 / 64] voxels an update hit; all zero between updates
     void* tab = nullptr;                  // an update's table: prefix, first triangle and id per named object,
     void* h_tab = nullptr;                // then the poses (device; pinned host staging of the same layout)
@@ -278,9 +280,9 @@ struct Cutout {
 // and the ray-reorder buffers belong to the stream, not to the context.
 // (vct_mixed.hip adds three: the plane a cone selection does not ask for, the upsample's hole
 // mask and row counts, and the frame call's low and hole frames; vct_temporal.hip one: the
-// per-wave stats words)
+// per-wave stats words; vct_motion.hip one: the per-object flags and its per-wave stats words)
 enum { kScFlags = 0, kScHand = 1, kScKeys = 2, kScSort = 3, kScOrder = 4, kScUnsel = 5, kScMixUp = 6, kScMixed = 7,
-       kScTemporal = 8, kScN = 9 };
+       kScTemporal = 8, kScMotion = 9, kScN = 10 };
 struct StreamScratch {
     hipStream_t s = nullptr;
     bool used = false;
@@ -607,6 +609,8 @@ void dynamic_free(vct_ctx* c);
 inline bool objects_live(const vct_ctx* c) { return c->obj.live && c->obj.epoch == c->grid_epoch; }
 inline bool layer_in_place(const vct_ctx* c) { return dynamic_live(c) && c->dyn.layer[c->dyn.cur].n_tri > 0; }
 void objects_free(vct_ctx* c);
+// vct_motion.hip: poses[ids[j]] = src[j] for the n objects an update named (all device pointers)
+void objects_scatter_poses(hipStream_t s, const uint32_t* ids, const void* src, uint32_t n, void* poses);
 // the triangles of Mesh::tri that the last vct_voxelize* put there
 inline uint32_t static_triangles(const vct_ctx* c) {
     return objects_live(c) ? c->obj.n_static : dynamic_live(c) ? c->dyn.n_static : c->mesh.n_tri;

@@ -24,6 +24,8 @@
 //   k_obj_list        the mask's bits as the fix-up list; the mask is cleared word by word on
 //                     the way (it is all zero between updates).
 //   k_dyn_fixup, k_dyn_occ_list, K3's live blocks: the layer's (vct_dynamic_sat.h).
+//   k_obj_scatter_poses (vct_motion.hip): the update's poses into the set's per-object array,
+//                     which include/vct_motion.h reads; queued before the wait.
 // One wait for the stream, at the end: the redo flag, the stats and K3's live-block count.
 // Redo, when only a subset moved: retract what this update added (the slots from M on, packed),
 // k_dyn_unpack the occupied records, add those slots again in the seven-atomic form, fix the
@@ -284,6 +286,11 @@ vct_status objects_move(vct_ctx* c, const uint32_t* ids, uint32_t n, const ObjPo
     hipLaunchKernelGGL(k_dyn_occ_list, dim3(wb), dim3(256), 0, s, g.occ_bits, nwords, g.occ_list, g.occ_count);
     if ((e = hipGetLastError()) != hipSuccess) return lhip(c, e, "objects_update");
     if ((e = launch_k3_live(c)) != hipSuccess) return lhip(c, e, "K3 live blocks");
+    // the set remembers the poses (vct_motion.h); queued before the wait, which is what lets the
+    // caller of the device form reuse its poses once the call has returned.  An update that fails
+    // after this point has written the array already; it leaves `live` false, so nothing reads it
+    objects_scatter_poses(s, d_tab + 2 * n + 1, poses, n, o.poses);
+    if ((e = hipGetLastError()) != hipSuccess) return lhip(c, e, "objects_update: poses");
     if ((e = hipMemcpyAsync(o.h_head, head, sizeof(DynHead), hipMemcpyDeviceToHost, s)) != hipSuccess) return lhip(c, e, "read back");
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return lhip(c, e, "objects_update sync");
     const DynHead h = *(const DynHead*)o.h_head;
@@ -312,7 +319,8 @@ vct_status objects_move(vct_ctx* c, const uint32_t* ids, uint32_t n, const ObjPo
 }
 
 void release(Objects& o) {
-    for (void* p : {(void*)o.pos, (void*)o.idx, (void*)o.mat, (void*)o.kd, o.rec, (void*)o.vis, (void*)o.mask, o.tab})
+    for (void* p : {(void*)o.pos, (void*)o.idx, (void*)o.mat, (void*)o.kd, o.rec, (void*)o.vis, (void*)o.mask, o.tab, o.poses,
+                    (void*)o.d_first})
         if (p) (void)hipFree(p);
     if (o.h_tab) (void)hipHostFree(o.h_tab);
     if (o.h_head) (void)hipHostFree(o.h_head);
@@ -425,7 +433,9 @@ extern "C" vct_status vct_objects_define(vct_ctx* c, const vct_object_mesh* mesh
         {(void**)&o.pos, pos.size() * 4, pos.data()},  {(void**)&o.idx, idx.size() * 4, idx.data()},
         {(void**)&o.mat, mat.size() * 4, mat.data()},  {(void**)&o.kd, kd4 ? (size_t)n_mat * 16 : 0, kd4},
         {&o.rec, rec_bytes, nullptr},                  {(void**)&o.vis, (size_t)n_objects * 4, nullptr},
-        {(void**)&o.mask, nwords * 8, nullptr},        {&o.tab, tab_bytes(n_objects), nullptr}};
+        {(void**)&o.mask, nwords * 8, nullptr},        {&o.tab, tab_bytes(n_objects), nullptr},
+        {&o.poses, sizeof(ObjPose) * (size_t)n_objects, nullptr},
+        {(void**)&o.d_first, ((size_t)n_objects + 1) * 4, o.first.data()}};
     vct_status st = VCT_OK;
     for (const auto& d : dev) {
         if (!d.bytes) continue;

@@ -8,7 +8,7 @@
 //                [--light SPEC]... [--shadow-tan T] [--sky Z[:H[:G]]] [--env FILE[:SCALE]] [--sky-view] [--mixed 2|4]
 //                [--fog DENSITY] [--temporal N] [--probes D] [--present CURVE[:auto|:E][:bloom]]
 //                [--dynamic FILE.obj [--dynamic-offset x,y,z]]
-//                [--object FILE.obj[@x,y,z]]...
+//                [--object FILE.obj[@x,y,z]]... [--object-step x,y,z] [--no-object-motion]
 //                [--voxels LEVEL[:MODE]]...
 //   (devices > 1: one process drives that many GPUs through vct_create_multi)
 //   --model: the model matrix of the reference's draw, T(0,-1.75,0) S(0.2)
@@ -71,6 +71,12 @@
 //            applied after the model matrix of --model.  The set is registered once in object
 //            space and the device applies each matrix; Kd materials only.  Exclusive with
 //            --dynamic;
+//   --object-step: x,y,z: every --object advances by this much per frame (frame f shows it at its
+//            offset + f x step; only the moved objects are voxelized again).  With --temporal N and
+//            --shaded the frame loop also runs vct_objects_motion_device (include/vct_motion.h) and
+//            hands its two planes to the accumulate, so a moving object keeps its history;
+//            --no-object-motion leaves that call out (the accumulate then runs as if nothing had
+//            moved), for comparing the two;
 //   --light:  one light of a light list (include/vct_lights.h), repeatable, in list order; with
 //            any --light the list replaces the default directional light.  SPEC is colon-
 //            separated fields of comma-separated floats, world units, angles in degrees:
@@ -291,6 +297,8 @@ int main(int argc, char** argv) {
     float dyn_offset[3] = {0.0f, 0.0f, 0.0f};
     struct ObjectArg { std::string file; float offset[3]; };
     std::vector<ObjectArg> objects;
+    float object_step[3] = {0.0f, 0.0f, 0.0f};
+    bool has_step = false, object_motion = true;
     bool ref_model = true, fit_grid = true;
     int bounces = 0;
     std::string linear;
@@ -404,6 +412,12 @@ int main(int argc, char** argv) {
             if (dynamic.empty() || dynamic.rfind("--", 0) == 0) { std::fprintf(stderr, "--dynamic needs a file (--dynamic FILE.obj)\n"); return 2; }
             has_dynamic = true;
         }
+        else if (a == "--no-object-motion") object_motion = false;
+        else if (a == "--object-step" || a.rfind("--object-step=", 0) == 0) {
+            const std::string spec = a == "--object-step" ? (i + 1 < argc ? argv[++i] : "") : a.substr(14);
+            if (!parse_offset(spec, object_step)) { std::fprintf(stderr, "malformed --object-step %s\n", spec.c_str()); return 2; }
+            has_step = true;
+        }
         else if (a == "--object" || a.rfind("--object=", 0) == 0) {
             const std::string spec = a == "--object" ? (i + 1 < argc ? argv[++i] : "") : a.substr(9);
             ObjectArg o{spec.substr(0, spec.rfind('@')), {0.0f, 0.0f, 0.0f}};
@@ -421,7 +435,7 @@ int main(int argc, char** argv) {
     if (pos.empty()) {
         std::fprintf(stderr, "usage: %s model.obj [grid] [width] [height] [frames] [out.ppm] [devices] "
                              "[--model=reference|identity] [--grid=fit|unit] [--bounces N] [--linear=frame.f32] [--shadow-tan T] [--sky Z[:H[:G]]] [--env FILE[:SCALE]] [--sky-view] [--shaded] [--cutouts[=CUTOFF]] [--mixed 2|4] [--fog DENSITY] [--temporal N] [--probes D] [--present CURVE[:auto|:E][:bloom]] [--voxels LEVEL[:MODE]]... "
-                             "[--dynamic FILE.obj [--dynamic-offset x,y,z]] [--object FILE.obj[@x,y,z]]... "
+                             "[--dynamic FILE.obj [--dynamic-offset x,y,z]] [--object FILE.obj[@x,y,z]]... [--object-step x,y,z] [--no-object-motion] "
                              "[--light dir:d:rgb | point:p:rgb:range | spot:p:d:rgb:range:inner:outer]...\n",
                      argv[0]);
         return 2;
@@ -438,6 +452,7 @@ int main(int argc, char** argv) {
     if (!(shadow_tan >= 0.0f) || !std::isfinite(shadow_tan)) { std::fprintf(stderr, "--shadow-tan must be finite and >= 0\n"); return 2; }
     if (has_offset && !has_dynamic) { std::fprintf(stderr, "--dynamic-offset needs --dynamic FILE.obj\n"); return 2; }
     if (has_dynamic && !objects.empty()) { std::fprintf(stderr, "--object and --dynamic exclude each other\n"); return 2; }
+    if (has_step && objects.empty()) { std::fprintf(stderr, "--object-step needs --object FILE.obj[@x,y,z]\n"); return 2; }
     s.bounces = (uint32_t)bounces;
     s.shadow_tan = shadow_tan;
     s.lights = lights;
@@ -453,6 +468,7 @@ int main(int argc, char** argv) {
     s.mixed_factor = mixed;
     s.fog_density = fog_density;
     s.temporal_len = temporal;
+    s.object_motion = object_motion;
     s.probes = probes;
     s.present = present.on;
     s.present_curve = present.curve;
@@ -511,10 +527,21 @@ int main(int argc, char** argv) {
     auto r = std::make_shared<ConeTraceRenderer>("test", s);
     A.renderers["ConeTrace"] = r;
     for (int f = 0; f < frames; ++f) {
+        if (has_step && f > 0) {   // every object advances by the step: frame f shows offset + f * step
+            for (size_t k = 0; k < s.objects.size(); ++k) {
+                float m[16];
+                for (int i = 0; i < 16; ++i) m[i] = s.objects[k].matrix[i];
+                for (int j = 0; j < 3; ++j) m[12 + j] = s.objects[k].matrix[12 + j] + (float)f * object_step[j];
+                r->SetObjectMatrix(k, m);
+            }
+        }
         A.renderers["ConeTrace"]->Render();                   // engine.cpp:151
         if (!r->ok()) return 1;
         std::printf("frame %d: K4 %.3f ms, %llu cone steps, %.1f Mcone-steps/s\n", f, r->last_trace_ms(),
                     r->last_cone_steps(), r->last_cone_steps() / (r->last_trace_ms() * 1e3));
+        uint32_t ms[4];
+        if (r->last_motion(ms))    // object motion ran (--temporal, --shaded and --object together)
+            std::printf("frame %d: motion valid %u still %u moved %u appeared %u\n", f, ms[0], ms[1], ms[2], ms[3]);
     }
     if (!r->WritePPM(out)) return 1;
     if (!linear.empty() && !r->WriteLinear(linear)) return 1;

@@ -56,6 +56,7 @@ ConeTraceRenderer::~ConeTraceRenderer() {
     for (void* p : hist_) if (p) vct_device_free(ctx_, p);
     for (void* p : hist_len_) if (p) vct_device_free(ctx_, p);
     for (void* p : prev_gb_) if (p) vct_device_free(ctx_, p);
+    for (void* p : {tri_id_, bary_, motion_, pnrm_, pose_snap_, motion_stats_dev_}) if (p) vct_device_free(ctx_, p);
     vct_destroy(ctx_);
 }
 
@@ -172,6 +173,7 @@ bool ConeTraceRenderer::define_objects() {
     if (!check(vct_objects_define(ctx_, meshes.data(), (uint32_t)n, kd4.empty() ? nullptr : kd4.data(), (uint32_t)(kd4.size() / 4)),
                "vct_objects_define"))
         return false;
+    has_snap_ = false;                  // a new set: the snapshot describes the old one
     object_dirty_.assign(n, 1);
     return update_objects();
 }
@@ -296,19 +298,33 @@ void ConeTraceRenderer::Render() {
         std::swap(gb_[1], prev_gb_[1]);
     }
     if (s_.shaded && !ks_ && !check(vct_device_alloc(ctx_, (size_t)s_.width * s_.height * 16, &ks_), "alloc ks plane")) return;
+    const bool track = s_.temporal_len && s_.shaded && !s_.objects.empty() && s_.object_motion;   // object motion (renderer.h)
+    if (track && !tri_id_) {
+        const size_t px = (size_t)s_.width * s_.height;
+        if (!check(vct_device_alloc(ctx_, px * 4, &tri_id_), "alloc tri_id plane") ||
+            !check(vct_device_alloc(ctx_, px * 8, &bary_), "alloc bary plane") ||
+            !check(vct_device_alloc(ctx_, px * 16, &motion_), "alloc motion plane") ||
+            !check(vct_device_alloc(ctx_, px * 16, &pnrm_), "alloc previous-normal plane") ||
+            !check(vct_device_alloc(ctx_, 16, &motion_stats_dev_), "alloc motion stats"))
+            return;
+    }
+    uint32_t* const tri_id = track ? (uint32_t*)tri_id_ : nullptr;
+    float* const bary = track ? (float*)bary_ : nullptr;
+    motion_ran_ = false;
     if (vct_cutout_materials(ctx_) > 0) {   // a cutout mesh: the masked pass, flat or shaded records
         if (!check(vct_gbuffer_cutout_device(ctx_, &vc, s_.width, s_.height, s_.roughness, (float*)gb_[0], (float*)gb_[1],
-                                             (float*)gb_[2], s_.shaded ? (float*)ks_ : nullptr, nullptr, nullptr, nullptr),
+                                             (float*)gb_[2], s_.shaded ? (float*)ks_ : nullptr, nullptr, tri_id, bary),
                    "cutout G-buffer"))
             return;
     } else if (s_.shaded) {
         if (!check(vct_gbuffer_shaded_device(ctx_, &vc, s_.width, s_.height, s_.roughness, (float*)gb_[0], (float*)gb_[1],
-                                             (float*)gb_[2], (float*)ks_, nullptr, nullptr, nullptr), "shaded G-buffer"))
+                                             (float*)gb_[2], (float*)ks_, nullptr, tri_id, bary), "shaded G-buffer"))
             return;
     } else if (!check(vct_gbuffer_raster_device(ctx_, &vc, s_.width, s_.height, s_.roughness, (float*)gb_[0],
                                                 (float*)gb_[1], (float*)gb_[2]), "G-buffer")) {
         return;
     }
+    if (track && has_prev_ && has_snap_ && !object_motion()) return;
     unsigned long long zero = 0;
     if (!check(vct_memcpy(ctx_, counter_, &zero, 8, 0), "reset counter")) return;
     vct_trace_args a{};
@@ -357,6 +373,36 @@ void ConeTraceRenderer::Render() {
     if (s_.shaded && status_ == VCT_OK)
         check(vct_specular_tint_device(ctx_, a.spec4, (const float*)ks_, s_.width, s_.height, a.spec4), "vct_specular_tint_device");
     if (s_.temporal_len && status_ == VCT_OK) accumulate_diffuse();
+    if (track && status_ == VCT_OK) {   // the snapshot: this frame's poses are the next frame's previous ones
+        if (snap_objects_ < s_.objects.size()) {
+            if (pose_snap_) vct_device_free(ctx_, pose_snap_);
+            pose_snap_ = nullptr;
+            if (!check(vct_device_alloc(ctx_, s_.objects.size() * sizeof(vct_object_pose), &pose_snap_), "alloc pose snapshot")) return;
+            snap_objects_ = s_.objects.size();
+        }
+        if (!check(vct_objects_poses_device(ctx_, (vct_object_pose*)pose_snap_, (uint32_t)snap_objects_), "vct_objects_poses_device"))
+            return;
+        has_snap_ = true;
+        if (motion_ran_) check(vct_memcpy(ctx_, motion_stats_, motion_stats_dev_, 16, 1), "read motion stats");
+    }
+}
+
+bool ConeTraceRenderer::object_motion() {
+    vct_motion_args m{};
+    m.width = s_.width;
+    m.height = s_.height;
+    m.pos4 = (const float*)gb_[0];
+    m.nrm4 = (const float*)gb_[1];
+    m.tri_id = (const uint32_t*)tri_id_;
+    m.bary2 = (const float*)bary_;
+    m.prev_poses = (const vct_object_pose*)pose_snap_;
+    m.n_prev = (uint32_t)s_.objects.size();
+    m.motion4 = (float*)motion_;
+    m.prev_nrm4 = (float*)pnrm_;
+    m.stats = (uint32_t*)motion_stats_dev_;
+    if (!check(vct_objects_motion_device(ctx_, &m), "vct_objects_motion_device")) return false;
+    motion_ran_ = true;
+    return true;
 }
 
 bool ConeTraceRenderer::accumulate_diffuse() {
@@ -369,6 +415,10 @@ bool ConeTraceRenderer::accumulate_diffuse() {
     t.height = s_.height;
     t.pos4 = (const float*)gb_[0];
     t.nrm4 = (const float*)gb_[1];
+    if (motion_ran_) {   // the tap tests read the normals under the last frame's poses; prev_gb_ keeps the real ones
+        t.motion4 = (const float*)motion_;
+        t.nrm4 = (const float*)pnrm_;
+    }
     if (has_prev_) {
         t.prev_cam = &prev_cam_;
         t.prev_pos4 = (const float*)prev_gb_[0];

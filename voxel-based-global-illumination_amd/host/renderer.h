@@ -117,6 +117,10 @@ struct ConeTraceSettings {
         float matrix[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     };
     std::vector<Object> objects;
+    // with temporal_len > 0, shaded and objects: run vct_objects_motion_device every frame and hand
+    // its planes to the accumulate (include/vct_motion.h).  false: the accumulate runs without
+    // them, as if nothing had moved -- for comparing the two
+    bool object_motion = true;
 };
 
 class ConeTraceRenderer : public Renderer {
@@ -134,6 +138,8 @@ public:
     const std::string& error() const { return error_; }
     double last_trace_ms() const { return last_ms_; }
     unsigned long long last_cone_steps() const { return last_steps_; }
+    // object motion ran in the last Render() (below); its {valid, static_or_unmoved, moved, appeared}
+    bool last_motion(uint32_t out[4]) const { for (int k = 0; k < 4; ++k) out[k] = motion_stats_[k]; return motion_ran_; }
     // composite + present (vct_composite_device: direct + albedo * indirect + specular) -> binary PPM
     // With ConeTraceSettings::present the bytes are vct_present_device's, and a path ending in .png
     // is written as a PNG (RGB)
@@ -186,6 +192,21 @@ private:
     vct_camera prev_cam_{};
     bool has_prev_ = false;               // prev_gb_, prev_cam_ and hist_[1 - hist_cur_] hold a frame
     int hist_cur_ = 0;
+    // object motion (include/vct_motion.h), with temporal_len > 0, shaded and a set of objects: the
+    // shaded pass also writes tri_id and bary2, vct_objects_motion_device turns them and the pose
+    // snapshot of the last frame's end into motion4 and the previous-pose normal plane, the
+    // accumulate reads both, and the snapshot is taken again after it
+    bool object_motion();
+    void* tri_id_ = nullptr;
+    void* bary_ = nullptr;
+    void* motion_ = nullptr;
+    void* pnrm_ = nullptr;
+    void* pose_snap_ = nullptr;
+    void* motion_stats_dev_ = nullptr;
+    size_t snap_objects_ = 0;             // records pose_snap_ holds
+    bool has_snap_ = false;               // pose_snap_ holds the poses of the last frame's end, of this set
+    bool motion_ran_ = false;             // motion_ and pnrm_ are this frame's
+    uint32_t motion_stats_[4] = {0, 0, 0, 0};
     bool scene_dirty_ = true;
     bool dynamic_dirty_ = true;           // the dynamic matrix changed since the layer was voxelized
     std::vector<char> object_dirty_;      // per object: its matrix changed since the last update

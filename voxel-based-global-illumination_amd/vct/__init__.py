@@ -1309,6 +1309,42 @@ class Context:
         self._check(fn(self.h, C.byref(st)), "objects_stats")
         return {k: int(getattr(st, k)) for k, _ in _lib.VctObjectsStats._fields_ if k != "reserved"}
 
+    # -- object motion (include/vct_motion.h) ---------------------------------
+    @staticmethod
+    def _pose_records(poses, what: str) -> int:
+        """How many 80-byte pose records a [n, 20] float32 / [n, 80] uint8 device tensor holds."""
+        per = {"torch.float32": 20, "torch.uint8": 80}.get(str(poses.dtype))
+        if per is None or poses.dim() != 2 or poses.shape[1] != per:
+            raise VctError(_EINVAL, f"{what}: poses must be [n, 20] float32 or [n, 80] uint8, got "
+                                    f"{tuple(poses.shape)} {poses.dtype}")
+        return int(poses.shape[0])
+
+    def objects_poses_device(self, out):
+        """vct_objects_poses_device: queue a copy of the set's current poses (the last pose given
+        to each object, all zero for one never posed) into `out`, a device tensor [n, 20] float32
+        or [n, 80] uint8 with n >= n_objects.  Never waits."""
+        fn = _lib.bind_motion_extension(self.lib, "vct_objects_poses_device")
+        n = self._pose_records(out, "objects_poses_device")
+        self._check(fn(self.h, self._dev(out, "out", ("torch.float32", "torch.uint8")), n), "objects_poses_device")
+
+    def objects_motion_device(self, width, height, pos4, tri_id, bary2, prev_poses, motion4, nrm4=None, prev_nrm4=None,
+                              stats=None, n_prev=None):
+        """vct_objects_motion_device: motion4 (and prev_nrm4 from nrm4, both or neither) for this
+        frame's shaded-pass planes from `prev_poses`, the set's poses at last frame's end (a device
+        tensor as objects_poses_device fills it; n_prev: its record count unless given).
+        stats: None, or 4 int32 {valid, static_or_unmoved, moved, appeared}."""
+        fn = _lib.bind_motion_extension(self.lib, "vct_objects_motion_device")
+        n = width * height
+        a = _lib.VctMotionArgs()
+        a.width, a.height = width, height
+        a.pos4, a.nrm4 = self._dev(pos4, "pos4", _F32, 4 * n), self._dev(nrm4, "nrm4", _F32, 4 * n)
+        a.tri_id, a.bary2 = self._dev(tri_id, "tri_id", _I32, n), self._dev(bary2, "bary2", _F32, 2 * n)
+        a.n_prev = self._pose_records(prev_poses, "objects_motion_device") if n_prev is None else n_prev
+        a.prev_poses = self._dev(prev_poses, "prev_poses", ("torch.float32", "torch.uint8"))
+        a.motion4, a.prev_nrm4 = self._dev(motion4, "motion4", _F32, 4 * n), self._dev(prev_nrm4, "prev_nrm4", _F32, 4 * n)
+        a.stats = self._dev(stats, "stats", _I32, 4)
+        self._check(fn(self.h, C.byref(a)), "objects_motion_device")
+
     # -- grid access ------------------------------------------------------
     def download_level(self, level: int, face: int = 0) -> np.ndarray:
         nl, _ = self.level_dims(level)

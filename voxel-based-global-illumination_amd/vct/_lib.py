@@ -106,6 +106,9 @@ VCT_SHADING_FLIP_GREEN = 1
 CUTOUT_EXTENSIONS = ("vct_voxelize_cutout", "vct_voxelize_cutout_device", "vct_gbuffer_cutout_device",
                      "vct_cutout_materials")
 
+# include/vct_motion.h: object motion, likewise HIP only (bind_motion_extension)
+MOTION_EXTENSIONS = ("vct_objects_poses_device", "vct_objects_motion_device")
+
 # include/vct_present.h: the HDR present, likewise HIP only (bind_present_extension)
 PRESENT_EXTENSIONS = ("vct_luminance_meter_device", "vct_exposure_update_device", "vct_bloom_scratch_bytes",
                       "vct_bloom_device", "vct_present_device")
@@ -918,6 +921,41 @@ def bind_temporal_extension(lib: C.CDLL, name: str):
     except AttributeError:
         raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
                              "(include/vct_temporal.h is implemented by the HIP library only)") from None
+    fn.restype = res
+    fn.argtypes = args
+    return fn
+
+
+class VctMotionArgs(C.Structure):        # vct_motion_args
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("pos4", C.c_void_p),
+        ("nrm4", C.c_void_p),
+        ("tri_id", C.c_void_p),
+        ("bary2", C.c_void_p),
+        ("prev_poses", C.c_void_p),
+        ("n_prev", C.c_uint32),
+        ("motion4", C.c_void_p),
+        ("prev_nrm4", C.c_void_p),
+        ("stats", C.c_void_p),
+    ]
+
+
+def bind_motion_extension(lib: C.CDLL, name: str):
+    """The include/vct_motion.h function `name` of `lib`, with its signature declared;
+    AttributeError (naming the library) if this implementation does not export it."""
+    P, u32, i32 = C.c_void_p, C.c_uint32, C.c_int32
+    sig = {
+        "vct_objects_poses_device": (i32, [P, P, u32]),
+        "vct_objects_motion_device": (i32, [P, C.POINTER(VctMotionArgs)]),
+    }
+    res, args = sig[name]
+    try:
+        fn = getattr(lib, name)
+    except AttributeError:
+        raise AttributeError(f"{getattr(lib, '_name', lib)} does not export {name} "
+                             "(include/vct_motion.h is implemented by the HIP library only)") from None
     fn.restype = res
     fn.argtypes = args
     return fn

@@ -37,6 +37,16 @@ class ShadingMaterial:
         return m
 
 
+def set_flat(ctx, verts, idx, roughness: float) -> None:
+    """A shading set with every attribute absent and one material of the call's roughness and
+    Ks 1, on the static mesh (verts, idx) that `ctx` was voxelized with.  With it
+    vct_gbuffer_shaded_device equals vct_gbuffer_raster_device in every bit of pos4, nrm4 and
+    alb4 (vct_spec.h "shading attributes", last clause): the way to get the pass's tri_id and
+    bary2 planes -- what include/vct_motion.h reads -- for a scene without smooth normals."""
+    ctx.set_shading(verts, idx, None, [ShadingMaterial(roughness=roughness)], normal_offset=None, uv_offset=None,
+                    tangent_offset=None, bitangent_offset=None)
+
+
 def roughness_from_ns(ns) -> float:
     """clip(sqrt(2 / (ns + 2)), 0, 1): Ns = 0 is fully rough, a large Ns a mirror."""
     with np.errstate(all="ignore"):

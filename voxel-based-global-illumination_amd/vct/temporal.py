@@ -61,11 +61,13 @@ class History:
             return contextlib.nullcontext()
         return torch.cuda.stream(torch.cuda.ExternalStream(s))
 
-    def accumulate(self, gbuffer, camera, planes, motion=None):
+    def accumulate(self, gbuffer, camera, planes, motion=None, test_normals=None):
         """One frame.  gbuffer: (pos4, nrm4[, ...]) float32 device tensors [height, width, 4];
         camera: this frame's camera (a vct.camera.Camera or a VctCamera); planes: this frame's
         n_planes planes; motion: None, or motion4 (where each pixel's surface point was last
-        frame, w = 0: nowhere).  -> the accumulated planes."""
+        frame, w = 0: nowhere); test_normals: None, or the plane the accumulate's tap tests read
+        in place of nrm4 (vct.motion.MotionTracker's prev_nrm4: each pixel's normal under last
+        frame's pose) -- the history still stores the real nrm4.  -> the accumulated planes."""
         planes = list(planes)
         if len(planes) != self.n_planes:
             raise VctError(_EINVAL, f"History.accumulate: {len(planes)} planes, the history holds {self.n_planes}")
@@ -74,7 +76,7 @@ class History:
         old, new = self._cur, 1 - self._cur
         has = self._cam is not None
         self.ctx.temporal_accumulate_device(
-            self.params, pos4, nrm4, self.width, self.height, planes, self._planes[new], self._len[new],
+            self.params, pos4, nrm4 if test_normals is None else test_normals, self.width, self.height, planes, self._planes[new], self._len[new],
             prev_cam=self._cam, prev_pos4=self._gbuf[0] if has else None, prev_nrm4=self._gbuf[1] if has else None,
             hist=self._planes[old] if has else None, hist_len=self._len[old] if has else None, motion4=motion,
             stats=self.stats)
